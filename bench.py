@@ -1,8 +1,18 @@
 """bench.py -- BASELINE.json metric: GB/s of device-resident fp32 gradient buckets
 quantised + reduced (+ dequantised), 256 MiB per bucket, 1/2/4/8 GPUs.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run does what the headline needs and no more: it sets up, settles and
+warms up, times the K steps, writes the last timed step's result if
+--dump-outputs is given (DIR/out.npy, float32: the reduced bucket, or a fixed
+seeded lane sample of a large one -- dump_lanes), and prints the line (N > 1:
+the engine candidates are still verified and timed first, since the fastest
+verified one is the headline).  Everything else this file measures or checks
+-- the oracle parity checks, rooflines, per-stage times, CPU baselines, sizes,
+other precisions, the N > 1 sweep: the "Extra JSON fields" below -- runs only
+with --full, after the headline, and leaves the headline as it is.
 
 `python bench.py --gpus N` (N > 1, no WORLD_SIZE) starts its N ranks itself
 through torch.distributed.run before touching the GPU; WORLD_SIZE != --gpus is
@@ -27,7 +37,7 @@ and produces their allreduce over all ranks into a third buffer:
           hangs leaves the RCCL headline to the line keeper / watchdog.
 value = bucket bytes reduced per second over the whole job = N * R * 256 MiB / t.
 
-Extra JSON fields:
+Extra JSON fields (--full):
   roofline          N = 1: the fused kernel's HBM roofline (algorithmic bytes
                     (R+1)*4*n per launch, timed with HIP events on its own stream).
                     N > 1: the step's xGMI link roofline; the quant+sum kernel's
@@ -281,7 +291,7 @@ def oracle_check(srcs, out, lanes, k: int, rank: int, world: int, fmt: str = "f3
     return res
 
 
-def parse():
+def parse(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=50)
@@ -303,7 +313,44 @@ def parse():
                    help="N=1: skip the size list, cold-input run, numerics and host-memory (config 3) keys")
     p.add_argument("--grid-cap", type=int, default=0)
     p.add_argument("--json-out", default="")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="beyond the headline: the oracle parity checks, rooflines and per-stage times, and the extra "
+                        "keys (CPU baselines, sizes, other precisions, the N>1 sweep, ...); off, the run only sets "
+                        "up, warms up, times --steps steps and prints the line")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="after the timed steps, write what the last timed step computed to DIR/out.npy (float32; "
+                        "of a bucket above DUMP_MAX_ELEMS elements a fixed, seeded lane sample)")
+    a = p.parse_args(argv)
+    if a.steps < 1:
+        p.error("--steps must be at least 1")
+    return a
+
+
+# --dump-outputs: at most 2^23 fp32 values (32 MiB) of the reduced bucket
+DUMP_MAX_ELEMS = 1 << 23
+DUMP_SEED = 20240
+
+
+def dump_lanes(n: int) -> "np.ndarray | None":
+    """The lanes of an n-element result that --dump-outputs writes: all of
+    them (None) up to DUMP_MAX_ELEMS, else one lane out of each of
+    DUMP_MAX_ELEMS contiguous, near-equal parts of the bucket, at an offset
+    drawn from a fixed seed -- the same lanes in every run and every build,
+    in increasing order."""
+    import numpy as np
+    if n <= DUMP_MAX_ELEMS:
+        return None
+    edges = np.arange(DUMP_MAX_ELEMS + 1, dtype=np.int64) * n // DUMP_MAX_ELEMS
+    rng = np.random.default_rng(DUMP_SEED)
+    return edges[:-1] + (rng.random(DUMP_MAX_ELEMS) * (edges[1:] - edges[:-1])).astype(np.int64)
+
+
+def write_outputs(directory: str, arrays: dict) -> None:
+    """DIR/<name>.npy for every array the timed path returned (float32)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float32))
 
 
 def cpu_baseline(n_elems: int, R: int, k: int, seconds: float) -> dict:
@@ -1528,7 +1575,7 @@ def main():
                 print(f"rank {rank}: engine {eng} chunks {ch} {env} failed: {e}", file=sys.stderr, flush=True)
                 ok, err = 0, str(e)[:400]
             stages = None
-            if agree([0.0 if ok else 1.0], world)[0] == 0.0:   # every rank probes, or none does
+            if a.full and agree([0.0 if ok else 1.0], world)[0] == 0.0:   # every rank probes, or none does
                 try:
                     stages = stage_probe(comm, srcs, out, k, ch, stream, world)
                 except Exception as e:  # noqa: BLE001
@@ -1601,6 +1648,19 @@ def main():
         wall = time.perf_counter() - t0
         dev_ms = ev0.elapsed_time(ev1)
         wall = agree([wall], world)[0]
+        # --dump-outputs: what the last timed step left in `out` (every rank
+        # holds the same allreduce result; rank 0 writes it), taken before
+        # anything below runs another step
+        dump = None
+        if a.dump_outputs and rank == 0:
+            sel = dump_lanes(n)
+            dump = (out if sel is None else out.index_select(0, torch.from_numpy(sel).to(dev))).cpu().numpy()
+        if not a.full:   # the headline alone: no verification, parity or stage runs
+            for key in env:
+                os.environ.pop(key, None)
+            return {"engine": eng if world > 1 else "fused", "chunks": ch, "env": env,
+                    "ms_per_step": wall * 1e3 / a.steps, "settle_steps": settle_steps, "dev_ms": dev_ms,
+                    "verified": None, "parity": None, "stages": None, "dump": dump}
         # the timed steps' output against the reference engine's (N>1): the last
         # timed step's output, then four more steps alternating the two input
         # sets, each against the reference engine's results
@@ -1630,7 +1690,7 @@ def main():
             os.environ.pop(key, None)
         return {"engine": eng if world > 1 else "fused", "chunks": ch, "env": env, "ms_per_step": wall * 1e3 / a.steps,
                 "settle_steps": settle_steps, "dev_ms": dev_ms, "verified": verified, "parity": parity,
-                "stages": stages}
+                "stages": stages, "dump": dump}
 
     # dominant kernel alone: fused (N=1) or quant + local sum (N>1), HIP events
     # on its stream; timed once, right after the first headline measurement
@@ -1734,12 +1794,19 @@ def main():
             # N = 1: the fused kernel's HBM roofline.  N > 1: the step is bound by
             # the xGMI links, so `roofline` is the link fraction of the whole step
             # and the dominant HBM kernel's figure moves to `roofline_hbm_kernel`.
-            "roofline": kinfo["hbm"] if world == 1 else xgmi_roofline(world, n * 4, ms_per_step * 1e-3),
+            "roofline": kinfo.get("hbm") if world == 1 else xgmi_roofline(world, n * 4, ms_per_step * 1e-3),
             "cpu_baseline": None,
             "parity_vs_oracle": m["parity"],
             # the HIP / HSA / RCCL copies this rank is bound to (DESIGN.md "Runtimes")
             "runtime": runtime_libs(),
         }
+        res["full"] = a.full
+        if not a.full:
+            # a plain run measures the headline alone: the keys that take runs
+            # or checks of their own (--full) are not in its line
+            for key in ("roofline", "cpu_baseline", "parity_vs_oracle"):
+                del res[key]
+            return res
         if world == 1:
             res["roofline_cold"] = kinfo["cold"]
         if world > 1:
@@ -1786,7 +1853,7 @@ def main():
     def publish(res: dict, stage: str) -> None:
         """From now on every way the run can end prints `res`."""
         res["phase_s"] = PHASES
-        if world > 1 and not a.no_sweep:
+        if a.full and world > 1 and not a.no_sweep:
             res["sweep"] = SWEEP_ROWS
         RESULT[0] = res
         watchdog.on_fire = on_overrun
@@ -1817,7 +1884,8 @@ def main():
     if world == 1:
         with Phase("headline"):
             m = measure("fused", 1, {})
-            dominant_kernel()
+            if a.full:
+                dominant_kernel()
         measured.append((m, build_res(m)))
         publish(measured[-1][1], "headline measured")
     else:
@@ -1831,10 +1899,11 @@ def main():
         if best1 is not None:
             with Phase("headline_rccl"):
                 m = measure(best1[1], best1[2], best1[3])
-                dominant_kernel()
+                if a.full:
+                    dominant_kernel()
             measured.append((m, build_res(m)))
             publish(measured[-1][1], f"headline measured on {m['engine']}; RCCL sweep next")
-            if not a.no_sweep:
+            if a.full and not a.no_sweep:
                 for key in best1[3]:   # the sweep runs every engine with its defaults
                     os.environ.pop(key, None)
                 sweep_pass("sweep_rccl", lambda eng: eng == "rccl")
@@ -1857,11 +1926,11 @@ def main():
                 for key in best2[3]:
                     os.environ.pop(key, None)
             else:
-                if not kinfo:
+                if a.full and not kinfo:
                     dominant_kernel()
                 line = build_res(m)
                 # a phase-2 headline replaces phase 1's only if it was verified like it
-                ok = m["verified"] is not False and (m["parity"]["mismatches"] or 0) == 0
+                ok = m["verified"] is not False and ((m["parity"] or {}).get("mismatches") or 0) == 0
                 if agree([0.0 if ok else 1.0], world)[0] == 0.0:
                     measured.append((m, line))
         if not measured:
@@ -1872,7 +1941,8 @@ def main():
         best[1]["headline_candidates"] = [
             {"engine": mm["engine"], "chunks": mm["chunks"], "env": mm["env"] or None,
              "ms_per_step": round(mm["ms_per_step"], 4), "value": ln["value"],
-             "verified_vs_reference_engine": mm["verified"], "oracle_mismatches": mm["parity"]["mismatches"]}
+             "verified_vs_reference_engine": mm["verified"],
+             "oracle_mismatches": (mm["parity"] or {}).get("mismatches")}
             for mm, ln in measured]
         if phase2_error:
             best[1]["phase2_error"] = phase2_error
@@ -1884,10 +1954,16 @@ def main():
         os.environ.update(best[0]["env"])
     res = RESULT[0]
     chosen = ("fused", 1, {}) if world == 1 else (best[0]["engine"], best[0]["chunks"], dict(best[0]["env"]))
+    if a.dump_outputs and rank == 0:
+        # the headline measurement's last timed step, as its caller received it
+        set_stage("writing --dump-outputs")
+        with Phase("dump_outputs"):
+            write_outputs(a.dump_outputs, {"out": (measured[0] if world == 1 else best)[0]["dump"]})
+        set_stage("headline measured")
     if os.environ.get("INCCL_BENCH_TEST_DIE") == "1" and rank == 0:   # test hook: rank 0 dies after the headline
         import signal
         os.kill(os.getpid(), signal.SIGKILL)
-    if world > 1 and not a.no_sweep:
+    if a.full and world > 1 and not a.no_sweep:
         for key in chosen[2]:   # the sweep runs every engine with its defaults
             os.environ.pop(key, None)
         # The rest of the sweep and the bf16 key drive engines never before run
@@ -1954,7 +2030,7 @@ def main():
                 print(f"bench: extra key {key} failed: {e!r}", file=sys.stderr, flush=True)
                 res[key] = {"error": repr(e)}
 
-    if world == 1 and not a.no_extras:
+    if a.full and world == 1 and not a.no_extras:
         extra("host_e2e", lambda: host_e2e(comm, k))
         extra("api_allreduce_write", lambda: api_allreduce_write(comm))
         extra("sizes", lambda: n1_sizes(dev, R, k))
@@ -1965,7 +2041,7 @@ def main():
         extra("switch_batch", lambda: switch_batch(dev))
         extra("switch_batch_acks", lambda: switch_batch(dev, acks=True))
         extra("switch_nonroot_round", lambda: switch_nonroot_round(dev))
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         extra("cpu_baseline", lambda: cpu_baseline(n, R, k, a.cpu_seconds))
         extra("cpu_baseline_allcores", lambda: cpu_baseline_allcores(n, R, k, min(a.cpu_seconds, 5.0)))
         extra("cpu_reference_pipeline", lambda: cpu_reference_pipeline(min(a.cpu_seconds, 5.0)))

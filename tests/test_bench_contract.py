@@ -69,6 +69,37 @@ def test_oracle_check_world1_detects_mismatch(orc):
     assert b.oracle_check(srcs, out, lanes, 25, 0, 1)["mismatches"] == 1
 
 
+def test_full_and_dump_outputs_options():
+    """--full is off by default; --steps below 1 is refused."""
+    b = _bench()
+    a = b.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs == "" and a.steps == 7 and a.warmup == 2
+    a = b.parse(["--full", "--dump-outputs", "somewhere"])
+    assert a.full is True and a.dump_outputs == "somewhere"
+    with pytest.raises(SystemExit):
+        b.parse(["--steps", "0"])
+
+
+def test_dump_lanes_fixed_sample(tmp_path):
+    """--dump-outputs' lane sample: the whole bucket up to DUMP_MAX_ELEMS, above
+    it DUMP_MAX_ELEMS distinct increasing lanes spread over the whole bucket,
+    the same on every call; the files written are float32 and stay below 64 MB."""
+    import numpy as np
+    b = _bench()
+    M = b.DUMP_MAX_ELEMS
+    assert M * 4 <= 64_000_000
+    assert b.dump_lanes(1) is None and b.dump_lanes(M) is None
+    for n in (M + 1, 2 * M - 1, (256 << 20) // 4, (1 << 30) // 4 + 3):
+        lanes = b.dump_lanes(n)
+        assert lanes.shape == (M,) and lanes.dtype == np.int64
+        assert lanes[0] >= 0 and lanes[-1] < n and bool((np.diff(lanes) > 0).all())
+        assert lanes[-1] >= n - n // M - 1              # the last part of the bucket is sampled too
+        assert np.array_equal(lanes, b.dump_lanes(n))
+    b.write_outputs(str(tmp_path / "d"), {"out": np.arange(5, dtype=np.float64)})
+    got = np.load(tmp_path / "d" / "out.npy")
+    assert got.dtype == np.float32 and got.tolist() == [0.0, 1.0, 2.0, 3.0, 4.0]
+
+
 def test_world_size_mismatch_is_an_error():
     import os
     import subprocess

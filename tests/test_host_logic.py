@@ -51,12 +51,15 @@ def test_tcp_rendezvous(lib, world):
 def test_tcp_rendezvous_port_briefly_in_use(lib):
     """Rank 0's port is held by another socket for the first 1.5 s (as a port
     from the ephemeral range can be, as the local end of some connection): the
-    bind is retried until the boot deadline and the group still forms."""
+    bind is retried until the boot deadline and the group still forms.  The
+    holder is bound but does not listen, as such a local end does not: a
+    listening holder would accept rank 1's connection whenever rank 1 starts
+    inside the 1.5 s, and the test would then depend on how fast the ranks
+    start."""
     import time
     port = _free_port()
     holder = socket.socket()
     holder.bind(("0.0.0.0", port))
-    holder.listen(1)
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     ps = [ctx.Process(target=_boot_rank, args=(r, 2, port, q)) for r in range(2)]
