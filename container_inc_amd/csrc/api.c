@@ -275,8 +275,8 @@ struct inccl_op *inccl_op_create_allreduce_f32(struct inccl_communicator *comm, 
     return op;
 }
 
-static int allreduce_16(struct inccl_communicator *c, int kind, const uint16_t *const *srcs_dev, int R,
-                        uint16_t *dst_dev, size_t n, int scale_exp, void *stream);
+static int allreduce_any(struct inccl_communicator *c, int kind, const void *const *srcs, int R, void *dst, size_t n,
+                         int scale_exp, int chunks, void *stream);
 
 struct inccl_op *inccl_op_create_allreduce16(struct inccl_communicator *comm, int kind,
                                              const uint16_t *const *srcs_dev, int R, uint16_t *dst_dev, size_t n,
@@ -299,12 +299,9 @@ struct inccl_op *inccl_op_create_allreduce16(struct inccl_communicator *comm, in
 int inccl_op_run(struct inccl_op *op)
 {
     if (!op) return inccl_set_error(INCCL_ERR_ARG, "inccl_op_run: op is NULL");
-    if (op->comm && op->in_kind != INCCL_KIND_F32)
-        return allreduce_16(op->comm, op->in_kind, (const uint16_t *const *)op->srcs, op->R, (uint16_t *)op->dst, op->n,
-                            op->scale_exp, op->stream);
-    if (op->comm)
-        return inccl_allreduce_f32_pipelined(op->comm, (const float *const *)op->srcs, op->R, (float *)op->dst, op->n,
-                                             op->scale_exp, op->chunks, op->stream);
+    if (op->comm)   /* a 16-bit op's chunks stay 0: one piece */
+        return allreduce_any(op->comm, op->in_kind, op->srcs, op->R, op->dst, op->n, op->scale_exp, op->chunks,
+                             op->stream);
     return kerr(inccl_k_stream(op->in_kind, op->out_kind, op->srcs, op->R, op->dst, op->n, op->scale_exp, NULL,
                                op->scale_R, op->stream));
 }
@@ -335,25 +332,29 @@ int inccl_reduce_f32(const float *const *srcs_dev, int R, float *dst_dev, size_t
                            NULL, R, stream);
 }
 
+static int absmax_any(int kind, const void *const *srcs_dev, int R, size_t n, uint32_t *amax_bits_dev, int zero_first,
+                      void *stream)
+{
+    if (!srcs_dev) return inccl_set_error(INCCL_ERR_ARG, "srcs is NULL");
+    return kerr(inccl_k_absmax(kind, srcs_dev, R, n, amax_bits_dev, zero_first, stream));
+}
+
 int inccl_absmax_f32(const float *const *srcs_dev, int R, size_t n, uint32_t *amax_bits_dev, int zero_first,
                      void *stream)
 {
-    if (!srcs_dev) return inccl_set_error(INCCL_ERR_ARG, "srcs is NULL");
-    return kerr(inccl_k_absmax(srcs_dev, R, n, amax_bits_dev, zero_first, stream));
+    return absmax_any(INCCL_KIND_F32, (const void *const *)srcs_dev, R, n, amax_bits_dev, zero_first, stream);
 }
 
 int inccl_absmax_f16(const uint16_t *const *srcs_dev, int R, size_t n, uint32_t *amax_bits_dev, int zero_first,
                      void *stream)
 {
-    if (!srcs_dev) return inccl_set_error(INCCL_ERR_ARG, "srcs is NULL");
-    return kerr(inccl_k_absmax_f16(srcs_dev, R, n, amax_bits_dev, zero_first, stream));
+    return absmax_any(INCCL_KIND_F16, (const void *const *)srcs_dev, R, n, amax_bits_dev, zero_first, stream);
 }
 
 int inccl_absmax_bf16(const uint16_t *const *srcs_dev, int R, size_t n, uint32_t *amax_bits_dev, int zero_first,
                       void *stream)
 {
-    if (!srcs_dev) return inccl_set_error(INCCL_ERR_ARG, "srcs is NULL");
-    return kerr(inccl_k_absmax_bf16(srcs_dev, R, n, amax_bits_dev, zero_first, stream));
+    return absmax_any(INCCL_KIND_BF16, (const void *const *)srcs_dev, R, n, amax_bits_dev, zero_first, stream);
 }
 
 int inccl_reduce_f32_auto(const float *const *srcs_dev, int R, float *dst_dev, size_t n, uint32_t *amax_word_dev,
@@ -878,90 +879,21 @@ int inccl_allreduce_q32(struct inccl_communicator *c, const int32_t *src_dev, in
     INCCL_ORDERED(c, stream, allreduce_q32_body(c, src_dev, dst_dev, n, stream));
 }
 
-/* Variant B: quant + local sum -> grouped ncclSend/Recv of
- * int32 shards -> this library's fused sum over the W received shards +
- * dequantise (the switch aggregate, non_termination_switch.c:361-363, fused with
- * the back stage) -> ncclAllGather.  `ws` holds W*shard (send) + W*shard (recv). */
-static int allreduce_piece_a2a(struct inccl_communicator *c, const float *const *srcs, int R, float *dst, size_t n,
-                               int k, const uint32_t *amax, int scale_R, int32_t *ws, float *fws, hipStream_t st)
-{
-    const int W = c->group->world_size, me = c->group->rank;
-    const size_t shard = inccl_shard_elems(n, W), total = shard * (size_t)W;
-    int32_t *qsend = ws, *qrecv = ws + total;
-    int rc = kerr(inccl_k_stream(INCCL_KIND_F32, INCCL_KIND_Q32, (const void *const *)srcs, R, qsend, n, k, amax,
-                                 scale_R, st));
-    if (rc) return rc;
-    if (total > n) INCCL_HIP(hipMemsetAsync(qsend + n, 0, (total - n) * sizeof(int32_t), st));
-    rc = inccl_rccl_alltoall_q32(c, qsend, qrecv, shard, st);
-    if (rc) return rc;
-    const void *parts[INCCL_MAX_LOCAL_INPUTS];
-    for (int j = 0; j < W; ++j) parts[j] = (j == me) ? (const void *)(qsend + (size_t)me * shard)
-                                                      : (const void *)(qrecv + (size_t)j * shard);
-    const size_t lo = (size_t)me * shard;
-    const int in_place = (total == n);
-    float *gather = in_place ? dst : fws;
-    rc = kerr(inccl_k_stream_s(INCCL_KIND_Q32, INCCL_KIND_F32, parts, W, gather + lo, shard, k, amax, scale_R,
-                               c->out_shift, st));
-    if (rc) return rc;
-    rc = inccl_tp_all_gather_f32(c, gather + lo, gather, shard, st);
-    if (rc) return rc;
-    if (!in_place) INCCL_HIP(hipMemcpyAsync(dst, fws, n * sizeof(float), hipMemcpyDeviceToDevice, st));
-    return 0;
-}
-
-/* One bucket piece: quant + local sum -> reduce-scatter -> dequant shard ->
- * all-gather.  `ws` holds W*shard + shard int32; `fws` (if the gather cannot
- * land in dst in place) W*shard fp32. */
-static int allreduce_piece(struct inccl_communicator *c, const float *const *srcs, int R, float *dst, size_t n,
-                           int k, const uint32_t *amax, int scale_R, int32_t *ws, float *fws, hipStream_t st)
-{
-    const int W = c->group->world_size, me = c->group->rank;
-    const size_t shard = inccl_shard_elems(n, W), total = shard * (size_t)W;
-    int32_t *qsend = ws, *qrecv = ws + total;
-    int si = stage_open(c, st);
-    int rc = kerr(inccl_k_stream(INCCL_KIND_F32, INCCL_KIND_Q32, (const void *const *)srcs, R, qsend, n, k, amax,
-                                 scale_R, st));
-    if (rc) return rc;
-    if (total > n) INCCL_HIP(hipMemsetAsync(qsend + n, 0, (total - n) * sizeof(int32_t), st));
-    stage_close(c, si, st, INCCL_STAGE_QUANT);
-    si = stage_open(c, st);
-    rc = inccl_tp_reduce_scatter_q32(c, qsend, qrecv, shard, st);
-    if (rc) return rc;
-    stage_close(c, si, st, INCCL_STAGE_RS);
-    const size_t lo = (size_t)me * shard;
-    const int in_place = (total == n);
-    float *gather = in_place ? dst : fws;
-    const void *s1[1] = {qrecv};
-    si = stage_open(c, st);
-    rc = kerr(inccl_k_stream_s(INCCL_KIND_Q32, INCCL_KIND_F32, s1, 1, gather + lo, shard, k, amax, scale_R,
-                               c->out_shift, st));
-    if (rc) return rc;
-    stage_close(c, si, st, INCCL_STAGE_DEQUANT);
-    si = stage_open(c, st);
-    rc = inccl_tp_all_gather_f32(c, gather + lo, gather, shard, st);
-    if (rc) return rc;
-    stage_close(c, si, st, INCCL_STAGE_AG);
-    if (!in_place) {
-        si = stage_open(c, st);
-        INCCL_HIP(hipMemcpyAsync(dst, fws, n * sizeof(float), hipMemcpyDeviceToDevice, st));
-        stage_close(c, si, st, INCCL_STAGE_COPY);
-    }
-    return 0;
-}
-
-/* The scale of one allreduce.  A fixed exponent passes through.  INCCL_SCALE_AUTO
+/* The scale of one collective.  A fixed exponent passes through.  INCCL_SCALE_AUTO
  * takes the absmax of the local buckets (kind F32, BF16 or F16) and its max over
  * the group (with bit 31 set when a rank saw a NaN or +-Inf and the
  * communicator propagates them, inccl_comm_set_nonfinite).  On the IPC engines that max is agreed on the host anyway (the node's
  * shared memory), so the host also picks the exponent (inccl_choose_scale, the
- * host twin of the kernels' choose_scale): *k_out, no device word, no copy
- * back.  Otherwise the max stays on the device (*amax_out) for the kernels to
+ * host twin of the kernels' choose_scale): sc->k, no device word, no copy
+ * back.  Otherwise the max stays on the device (sc->amax) for the kernels to
  * resolve. */
 static int resolve_scale(struct inccl_communicator *c, int kind, const void *const *srcs, int R, size_t n,
-                         int scale_exp, hipStream_t st, const uint32_t **amax_out, int *k_out)
+                         int scale_exp, hipStream_t st, struct inccl_scale *sc)
 {
-    *amax_out = NULL;
-    *k_out = scale_exp;
+    const int W = c->group->world_size;
+    sc->k = scale_exp;
+    sc->amax = NULL;
+    sc->R = R * W;
     if (scale_exp != INCCL_SCALE_AUTO) {
         if (scale_exp < INCCL_SCALE_MIN || scale_exp > INCCL_SCALE_MAX)
             return inccl_set_error(INCCL_ERR_ARG, "scale_exp %d out of range", scale_exp);
@@ -970,158 +902,192 @@ static int resolve_scale(struct inccl_communicator *c, int kind, const void *con
     const int zf = 1 | (c->nonfinite == INCCL_NONFINITE_NAN ? INCCL_ABSMAX_FLAG_NONFINITE : 0);
     int rc = inccl_ws_claim(c, st);   /* the max word is shared by every call */
     if (rc) return rc;
-    rc = kind == INCCL_KIND_BF16  ? inccl_absmax_bf16((const uint16_t *const *)srcs, R, n, c->d_words, zf, st)
-             : kind == INCCL_KIND_F16 ? inccl_absmax_f16((const uint16_t *const *)srcs, R, n, c->d_words, zf, st)
-                                      : inccl_absmax_f32((const float *const *)srcs, R, n, c->d_words, zf, st);
+    rc = absmax_any(kind, srcs, R, n, c->d_words, zf, st);
     if (rc) return rc;
-    const int W = c->group->world_size;
-    if (W > 1 && c->group->transport == INCCL_TRANSPORT_RCCL &&
-        (c->engine == INCCL_ENGINE_P2P || c->engine == INCCL_ENGINE_LL || c->engine == INCCL_ENGINE_MESH)) {
+    if (W > 1 && c->group->transport == INCCL_TRANSPORT_RCCL && inccl_engine_is_ipc(c->engine)) {
         uint32_t v = 0;
         INCCL_HIP(hipMemcpyAsync(&v, c->d_words, sizeof(v), hipMemcpyDeviceToHost, st));
         INCCL_HIP(hipStreamSynchronize(st));
         rc = inccl_group_allreduce_max_u32(c->group, &v);
         if (rc) return rc;
         int nonfinite = 0;
-        const int k_host = inccl_choose_scale_word(v, R * W, &nonfinite);
-        if (nonfinite) {   /* a non-finite input somewhere (INCCL_NONFINITE_NAN): the kernels see the flag */
-            INCCL_HIP(hipMemcpyAsync(c->d_words, &v, sizeof(v), hipMemcpyHostToDevice, st));
-            INCCL_HIP(hipStreamSynchronize(st));
-            *amax_out = c->d_words;
-            *k_out = 0;
-            return 0;
-        }
-        *k_out = k_host;
-        return 0;
-    }
-    if (W > 1) {
+        sc->k = inccl_choose_scale_word(v, R * W, &nonfinite);
+        if (!nonfinite) return 0;
+        /* a non-finite input somewhere (INCCL_NONFINITE_NAN): the kernels see the flag */
+        INCCL_HIP(hipMemcpyAsync(c->d_words, &v, sizeof(v), hipMemcpyHostToDevice, st));
+        INCCL_HIP(hipStreamSynchronize(st));
+    } else if (W > 1) {
         rc = inccl_tp_allreduce_max_u32(c, c->d_words, 1, st);
         if (rc) return rc;
     }
-    *amax_out = c->d_words;
-    *k_out = 0;
+    sc->amax = c->d_words;
+    sc->k = 0;
     return 0;
 }
 
-int inccl_allreduce_f32(struct inccl_communicator *c, const float *const *srcs_dev, int R, float *dst_dev, size_t n,
-                        int scale_exp, void *stream)
-{
-    return inccl_allreduce_f32_pipelined(c, srcs_dev, R, dst_dev, n, scale_exp, 1, stream);
-}
+/* ---- the stages every sharded route is made of ---- */
 
-/* the rccl engine's small-bucket route: n int32 partials within rccl_ar_bytes
- * (INCCL_RCCL_AR_BYTES, default 1 MiB) go through one ncclAllReduce */
-static int rccl_small(const struct inccl_communicator *c, size_t n)
+/* quantise + local sum of the R buckets of `kind` into q[0, n), zeros up to `total` */
+static int quant_sum(int kind, const void *const *srcs, int R, int32_t *q, size_t n, size_t total,
+                     const struct inccl_scale *sc, hipStream_t st)
 {
-    return c->engine == INCCL_ENGINE_RCCL && c->group->transport == INCCL_TRANSPORT_RCCL &&
-           n <= c->rccl_ar_bytes / sizeof(int32_t);
-}
-
-static int allreduce_f32_body(struct inccl_communicator *c, const float *const *srcs_dev, int R, float *dst_dev,
-                              size_t n, int scale_exp, int chunks, void *stream)
-{
-    if (!c || !srcs_dev || R < 1 || R > INCCL_MAX_LOCAL_INPUTS || (!dst_dev && n))
-        return inccl_set_error(INCCL_ERR_ARG, "bad allreduce_f32 args");
-    for (int r = 0; r < R; ++r)
-        if (!srcs_dev[r] && n) return inccl_set_error(INCCL_ERR_ARG, "srcs[%d] is NULL", r);
-    if (n == 0) return 0;
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    const int W = c->group->world_size;
-    const uint32_t *amax = NULL;
-    int k = 0;
-    int rc = resolve_scale(c, INCCL_KIND_F32, (const void *const *)srcs_dev, R, n, scale_exp, st, &amax, &k);
+    const int rc = kerr(inccl_k_stream(kind, INCCL_KIND_Q32, srcs, R, q, n, sc->k, sc->amax, sc->R, st));
     if (rc) return rc;
-    const int scale_R = R * W;
+    if (total > n) INCCL_HIP(hipMemsetAsync(q + n, 0, (total - n) * sizeof(int32_t), st));
+    return 0;
+}
 
-    if (W == 1 && !c->force_sharded)   /* one fused HBM pass: quant + sum + dequant */
-        return kerr(inccl_k_stream_s(INCCL_KIND_F32, INCCL_KIND_F32, (const void *const *)srcs_dev, R, dst_dev, n, k,
-                                     amax, scale_R, c->out_shift, st));
+static int stage_quant(struct inccl_communicator *c, int kind, const void *const *srcs, int R, int32_t *q, size_t n,
+                       size_t total, const struct inccl_scale *sc, hipStream_t st)
+{
+    const int si = stage_open(c, st);
+    const int rc = quant_sum(kind, srcs, R, q, n, total, sc, st);
+    if (rc) return rc;
+    stage_close(c, si, st, INCCL_STAGE_QUANT);
+    return 0;
+}
 
-    /* the IPC engines: the ll kernel for small buckets when the ll engine was
-     * chosen explicitly (ll.c), else the one-kernel mesh exchange (mesh.c) or the
-     * host-synchronised p2p exchange (p2p.c).  The p2p engine (and the automatic
-     * fallback to it when RCCL is unavailable) never routes to ll by itself. */
-    if ((c->engine == INCCL_ENGINE_P2P || c->engine == INCCL_ENGINE_LL || c->engine == INCCL_ENGINE_MESH) &&
-        c->group->transport == INCCL_TRANSPORT_RCCL) {
-        const int si = stage_open(c, st);
-        if (c->engine == INCCL_ENGINE_LL && n <= c->ll_max_bytes / sizeof(float) && W > 1)
-            rc = inccl_ll_piece(c, srcs_dev, R, dst_dev, n, k, amax, scale_R, 0, 0, st);
-        else if (c->engine == INCCL_ENGINE_MESH)
-            rc = inccl_mesh_piece(c, srcs_dev, R, dst_dev, n, k, amax, scale_R, st);
-        else
-            rc = inccl_p2p_piece(c, srcs_dev, R, dst_dev, n, k, amax, scale_R, st);
-        if (!rc) stage_close(c, si, st, INCCL_STAGE_IPC);
-        return rc;
+/* dst[0, n) = the reduced int32 partials q dequantised to `kind` */
+static int stage_dequant(struct inccl_communicator *c, int kind, const int32_t *q, void *dst, size_t n,
+                         const struct inccl_scale *sc, hipStream_t st)
+{
+    const void *s1[1] = {q};
+    const int si = stage_open(c, st);
+    const int rc = kerr(inccl_k_stream_s(INCCL_KIND_Q32, kind, s1, 1, dst, n, sc->k, sc->amax, sc->R, c->out_shift, st));
+    if (rc) return rc;
+    stage_close(c, si, st, INCCL_STAGE_DEQUANT);
+    return 0;
+}
+
+/* The AR route: quant + local sum -> the engine's in-place int32 allreduce
+ * (ncclAllReduce(int32, sum), the switch aggregate inside RCCL; the p2p exchange
+ * for the IPC engines) -> dst = elements [lo, lo + cnt) dequantised: the whole
+ * bucket for an allreduce, the own shard for a reduce-scatter. */
+static int allreduce_via_q32(struct inccl_communicator *c, int kind, const void *const *srcs, int R, void *dst,
+                             size_t n, size_t lo, size_t cnt, const struct inccl_scale *sc, hipStream_t st)
+{
+    int rc = inccl_ws_claim(c, st);
+    if (rc) return rc;
+    rc = inccl_ensure_dev(&c->d_q32, &c->d_q32_bytes, n * sizeof(int32_t));
+    if (rc) return rc;
+    int32_t *q = (int32_t *)c->d_q32;
+    rc = stage_quant(c, kind, srcs, R, q, n, n, sc, st);
+    if (rc) return rc;
+    const int si = stage_open(c, st);
+    rc = inccl_tp_allreduce_q32(c, q, q, n, st);
+    if (rc) return rc;
+    stage_close(c, si, st, INCCL_STAGE_AR);
+    return stage_dequant(c, kind, q + lo, dst, cnt, sc, st);
+}
+
+/* Variant B, fp32 only: quant + local sum -> grouped
+ * ncclSend/Recv of int32 shards -> this library's fused sum over the W received
+ * shards + dequantise (the switch aggregate, non_termination_switch.c:361-363,
+ * fused with the back stage) -> ncclAllGather.  d_q32 holds W*shard (send) +
+ * W*shard (recv). */
+static int allreduce_a2a(struct inccl_communicator *c, const void *const *srcs, int R, float *dst, size_t n,
+                         const struct inccl_scale *sc, hipStream_t st)
+{
+    const int W = c->group->world_size, me = c->group->rank;
+    if (W > INCCL_MAX_LOCAL_INPUTS)
+        return inccl_set_error(INCCL_ERR_ARG, "a2a engine sums at most %d shards", INCCL_MAX_LOCAL_INPUTS);
+    const size_t shard = inccl_shard_elems(n, W), total = shard * (size_t)W;
+    const int in_place = (total == n);
+    int rc = inccl_ws_claim(c, st);
+    if (rc) return rc;
+    rc = inccl_ensure_dev(&c->d_q32, &c->d_q32_bytes, 2 * total * sizeof(int32_t));
+    if (rc) return rc;
+    if (!in_place) {
+        rc = inccl_ensure_dev(&c->d_f32, &c->d_f32_bytes, total * sizeof(float));
+        if (rc) return rc;
     }
-    /* RCCL's own allreduce on the int32 partials: quant + local sum -> in-place
-     * ncclAllReduce(int32, sum) -> dequantise (the switch aggregate inside RCCL).
-     * The rccl engine takes it too for small buckets: one collective launch in
-     * place of two where latency, not bytes, sets the time. */
-    if (c->engine == INCCL_ENGINE_AR || rccl_small(c, n)) {
-        rc = inccl_ws_claim(c, st);
-        if (rc) return rc;
-        rc = inccl_ensure_dev(&c->d_q32, &c->d_q32_bytes, n * sizeof(int32_t));
-        if (rc) return rc;
-        int32_t *q = (int32_t *)c->d_q32;
-        int si = stage_open(c, st);
-        rc = kerr(inccl_k_stream(INCCL_KIND_F32, INCCL_KIND_Q32, (const void *const *)srcs_dev, R, q, n, k, amax,
-                                 scale_R, st));
-        if (rc) return rc;
-        stage_close(c, si, st, INCCL_STAGE_QUANT);
+    int32_t *qsend = (int32_t *)c->d_q32, *qrecv = qsend + total;
+    rc = quant_sum(INCCL_KIND_F32, srcs, R, qsend, n, total, sc, st);
+    if (rc) return rc;
+    rc = inccl_rccl_alltoall_q32(c, qsend, qrecv, shard, st);
+    if (rc) return rc;
+    const void *parts[INCCL_MAX_LOCAL_INPUTS];
+    for (int j = 0; j < W; ++j) parts[j] = (j == me) ? (const void *)(qsend + (size_t)me * shard)
+                                                      : (const void *)(qrecv + (size_t)j * shard);
+    const size_t lo = (size_t)me * shard;
+    float *gather = in_place ? dst : (float *)c->d_f32;
+    rc = kerr(inccl_k_stream_s(INCCL_KIND_Q32, INCCL_KIND_F32, parts, W, gather + lo, shard, sc->k, sc->amax, sc->R,
+                               c->out_shift, st));
+    if (rc) return rc;
+    rc = inccl_tp_all_gather(c, gather + lo, gather, shard, sizeof(float), st);
+    if (rc) return rc;
+    if (!in_place) INCCL_HIP(hipMemcpyAsync(dst, gather, n * sizeof(float), hipMemcpyDeviceToDevice, st));
+    return 0;
+}
+
+/* One bucket piece of the RSAG route, any kind: quant + local sum (on `qst`) ->
+ * int32 reduce-scatter -> dequantise the own shard to `kind` -> all-gather of
+ * es-byte elements -> copy out when the gather could not land in dst in place.
+ * `ws` holds W*shard + shard int32; `gws` (for a ragged n) W*shard elements.
+ * qst == st: a whole call on its stream.  Else the pipelined call's side
+ * stream: ev[1] carries the quantised chunk over to `st`. */
+static int allreduce_piece(struct inccl_communicator *c, int kind, const void *const *srcs, int R, void *dst,
+                           size_t n, const struct inccl_scale *sc, int32_t *ws, void *gws, hipStream_t qst,
+                           hipStream_t st)
+{
+    const int W = c->group->world_size, me = c->group->rank;
+    const size_t shard = inccl_shard_elems(n, W), total = shard * (size_t)W, es = kind == INCCL_KIND_F32 ? 4 : 2;
+    int32_t *qsend = ws, *qrecv = ws + total;
+    int rc = stage_quant(c, kind, srcs, R, qsend, n, total, sc, qst);
+    if (rc) return rc;
+    if (qst != st) {
+        INCCL_HIP(hipEventRecord(c->ev[1], qst));
+        INCCL_HIP(hipStreamWaitEvent(st, c->ev[1], 0));
+    }
+    int si = stage_open(c, st);
+    rc = inccl_tp_reduce_scatter_q32(c, qsend, qrecv, shard, st);
+    if (rc) return rc;
+    stage_close(c, si, st, INCCL_STAGE_RS);
+    const int in_place = (total == n);
+    char *gather = in_place ? (char *)dst : (char *)gws, *own = gather + (size_t)me * shard * es;
+    rc = stage_dequant(c, kind, qrecv, own, shard, sc, st);
+    if (rc) return rc;
+    si = stage_open(c, st);
+    rc = inccl_tp_all_gather(c, own, gather, shard, es, st);
+    if (rc) return rc;
+    stage_close(c, si, st, INCCL_STAGE_AG);
+    if (!in_place) {
         si = stage_open(c, st);
-        rc = inccl_tp_allreduce_q32(c, q, q, n, st);
-        if (rc) return rc;
-        stage_close(c, si, st, INCCL_STAGE_AR);
-        si = stage_open(c, st);
-        const void *s1[1] = {q};
-        rc = kerr(inccl_k_stream_s(INCCL_KIND_Q32, INCCL_KIND_F32, s1, 1, dst_dev, n, k, amax, scale_R,
-                                   c->out_shift, st));
-        stage_close(c, si, st, INCCL_STAGE_DEQUANT);
-        return rc;
+        INCCL_HIP(hipMemcpyAsync(dst, gather, n * es, hipMemcpyDeviceToDevice, st));
+        stage_close(c, si, st, INCCL_STAGE_COPY);
     }
-    if (c->engine == INCCL_ENGINE_A2A && c->group->transport == INCCL_TRANSPORT_RCCL) {
-        if (W > INCCL_MAX_LOCAL_INPUTS)
-            return inccl_set_error(INCCL_ERR_ARG, "a2a engine sums at most %d shards", INCCL_MAX_LOCAL_INPUTS);
-        const size_t shard = inccl_shard_elems(n, W), total = shard * (size_t)W;
-        rc = inccl_ws_claim(c, st);
-        if (rc) return rc;
-        rc = inccl_ensure_dev(&c->d_q32, &c->d_q32_bytes, 2 * total * sizeof(int32_t));
-        if (rc) return rc;
-        if (total != n) {
-            rc = inccl_ws_claim(c, st);
-            if (rc) return rc;
-            rc = inccl_ensure_dev(&c->d_f32, &c->d_f32_bytes, total * sizeof(float));
-            if (rc) return rc;
-        }
-        return allreduce_piece_a2a(c, srcs_dev, R, dst_dev, n, k, amax, scale_R, (int32_t *)c->d_q32,
-                                   (float *)c->d_f32, st);
-    }
-    /* chunk boundaries: multiples of W*64 elements so every chunk's shards are
-     * 256-B aligned inside dst; each chunk has its own workspace region */
+    return 0;
+}
+
+/* The RSAG route in `chunks` pieces.  Chunk boundaries are multiples of W*64
+ * elements so every chunk's shards are 256-B aligned inside dst; each chunk has
+ * its own workspace region. */
+static int allreduce_rsag(struct inccl_communicator *c, int kind, const void *const *srcs, int R, void *dst,
+                          size_t n, const struct inccl_scale *sc, int chunks, hipStream_t st)
+{
+    const int W = c->group->world_size;
+    const size_t es = kind == INCCL_KIND_F32 ? 4 : 2;
     if (chunks < 1) chunks = 1;
     const size_t unit = (size_t)W * 64;
     size_t per = ((n + (size_t)chunks - 1) / (size_t)chunks + unit - 1) / unit * unit;
     if (per == 0) per = unit;
-    size_t ws_elems = 0, fws_elems = 0;
+    size_t ws_elems = 0, gws_elems = 0;
     for (size_t off = 0; off < n; off += per) {
         const size_t cnt = (n - off) < per ? (n - off) : per;
         const size_t shard = inccl_shard_elems(cnt, W);
         ws_elems += shard * (size_t)W + shard;
-        if (shard * (size_t)W != cnt) fws_elems = shard * (size_t)W;
+        if (shard * (size_t)W != cnt) gws_elems = shard * (size_t)W;
     }
-    rc = inccl_ws_claim(c, st);
+    int rc = inccl_ws_claim(c, st);
     if (rc) return rc;
     rc = inccl_ensure_dev(&c->d_q32, &c->d_q32_bytes, ws_elems * sizeof(int32_t));
     if (rc) return rc;
-    if (fws_elems) {
-        rc = inccl_ws_claim(c, st);
-        if (rc) return rc;
-        rc = inccl_ensure_dev(&c->d_f32, &c->d_f32_bytes, fws_elems * sizeof(float));
+    if (gws_elems) {
+        rc = inccl_ensure_dev(&c->d_f32, &c->d_f32_bytes, gws_elems * es);
         if (rc) return rc;
     }
     int32_t *ws = (int32_t *)c->d_q32;
-    const float *sub[INCCL_MAX_LOCAL_INPUTS];
-    if (per >= n) return allreduce_piece(c, srcs_dev, R, dst_dev, n, k, amax, scale_R, ws, (float *)c->d_f32, st);
+    if (per >= n) return allreduce_piece(c, kind, srcs, R, dst, n, sc, ws, c->d_f32, st, st);
 
     /* pipelined: quantise chunk i+1 on the side stream while chunk i's
      * collectives run on `st` (RCCL kernels and the HBM-bound quantiser share
@@ -1131,267 +1097,181 @@ static int allreduce_f32_body(struct inccl_communicator *c, const float *const *
     stage_close(c, stage_open(c, st), st, INCCL_STAGE_KINDS);
     INCCL_HIP(hipEventRecord(c->ev[0], st));
     INCCL_HIP(hipStreamWaitEvent(c->side_stream, c->ev[0], 0));
+    const void *sub[INCCL_MAX_LOCAL_INPUTS];
     for (size_t off = 0; off < n; off += per) {
         const size_t cnt = (n - off) < per ? (n - off) : per;
-        const size_t shard = inccl_shard_elems(cnt, W), total = shard * (size_t)W;
-        for (int r = 0; r < R; ++r) sub[r] = srcs_dev[r] + off;
-        int32_t *qsend = ws, *qrecv = ws + total;
-        int si = stage_open(c, c->side_stream);
-        rc = kerr(inccl_k_stream(INCCL_KIND_F32, INCCL_KIND_Q32, (const void *const *)sub, R, qsend, cnt, k, amax,
-                                 scale_R, c->side_stream));
+        for (int r = 0; r < R; ++r) sub[r] = (const char *)srcs[r] + off * es;
+        rc = allreduce_piece(c, kind, sub, R, (char *)dst + off * es, cnt, sc, ws, c->d_f32, c->side_stream, st);
         if (rc) return rc;
-        if (total > cnt) INCCL_HIP(hipMemsetAsync(qsend + cnt, 0, (total - cnt) * sizeof(int32_t), c->side_stream));
-        stage_close(c, si, c->side_stream, INCCL_STAGE_QUANT);
-        INCCL_HIP(hipEventRecord(c->ev[1], c->side_stream));
-        INCCL_HIP(hipStreamWaitEvent(st, c->ev[1], 0));
-        si = stage_open(c, st);
-        rc = inccl_tp_reduce_scatter_q32(c, qsend, qrecv, shard, st);
-        if (rc) return rc;
-        stage_close(c, si, st, INCCL_STAGE_RS);
-        const int in_place = (total == cnt);
-        float *gather = in_place ? dst_dev + off : (float *)c->d_f32;
-        const size_t lo = (size_t)c->group->rank * shard;
-        const void *s1[1] = {qrecv};
-        si = stage_open(c, st);
-        rc = kerr(inccl_k_stream_s(INCCL_KIND_Q32, INCCL_KIND_F32, s1, 1, gather + lo, shard, k, amax, scale_R,
-                                   c->out_shift, st));
-        if (rc) return rc;
-        stage_close(c, si, st, INCCL_STAGE_DEQUANT);
-        si = stage_open(c, st);
-        rc = inccl_tp_all_gather_f32(c, gather + lo, gather, shard, st);
-        if (rc) return rc;
-        stage_close(c, si, st, INCCL_STAGE_AG);
-        if (!in_place) {
-            si = stage_open(c, st);
-            INCCL_HIP(hipMemcpyAsync(dst_dev + off, c->d_f32, cnt * sizeof(float), hipMemcpyDeviceToDevice, st));
-            stage_close(c, si, st, INCCL_STAGE_COPY);
-        }
-        ws += total + shard;
+        ws += inccl_shard_elems(cnt, W) * ((size_t)W + 1);
     }
     /* `st` already waited on every side-stream chunk */
     return 0;
 }
 
-int inccl_allreduce_f32_pipelined(struct inccl_communicator *c, const float *const *srcs_dev, int R, float *dst_dev,
-                                  size_t n, int scale_exp, int chunks, void *stream)
-{
-    INCCL_ORDERED(c, stream, allreduce_f32_body(c, srcs_dev, R, dst_dev, n, scale_exp, chunks, stream));
-}
+static const char *const kind_names[] = {"f32", "", "", "bf16", "f16"};
 
-/* 2-byte buckets (kind INCCL_KIND_BF16 or INCCL_KIND_F16): the fp32 path's
- * arithmetic on the widened values.  The int32 partial sums travel as in the
- * fp32 path (the switch's aggregate, nts.c:361-363); only the result's format
- * differs, so the "rccl" engine's all-gather moves 2 bytes per element instead
- * of 4 (an all-gather copies bytes: the same one serves both formats), and the
- * mesh and p2p engines' reduce kernels narrow to the bucket's format before
- * their result exchange. */
-static int allreduce_16_body(struct inccl_communicator *c, int kind, const uint16_t *const *srcs_dev, int R,
-                             uint16_t *dst_dev, size_t n, int scale_exp, void *stream)
+/* The allreduce of kind F32, BF16 or F16 buckets.  The int32 partial sums
+ * travel alike for every kind (the switch's aggregate, nts.c:361-363); only the
+ * result's format differs, so a 2-byte kind's all-gather moves 2 bytes per
+ * element instead of 4 (an all-gather copies bytes: the same one serves both),
+ * and the mesh and p2p engines' reduce kernels narrow to the bucket's format
+ * before their result exchange.  Which engine carries the bucket: inccl_route.h. */
+static int allreduce_body(struct inccl_communicator *c, int kind, const void *const *srcs, int R, void *dst, size_t n,
+                          int scale_exp, int chunks, void *stream)
 {
-    if (!c || !srcs_dev || R < 1 || R > INCCL_MAX_LOCAL_INPUTS || (!dst_dev && n))
-        return inccl_set_error(INCCL_ERR_ARG, "bad allreduce_%s args", kind == INCCL_KIND_F16 ? "f16" : "bf16");
+    if (!c || !srcs || R < 1 || R > INCCL_MAX_LOCAL_INPUTS || (!dst && n))
+        return inccl_set_error(INCCL_ERR_ARG, "bad allreduce_%s args", kind_names[kind]);
     for (int r = 0; r < R; ++r)
-        if (!srcs_dev[r] && n) return inccl_set_error(INCCL_ERR_ARG, "srcs[%d] is NULL", r);
+        if (!srcs[r] && n) return inccl_set_error(INCCL_ERR_ARG, "srcs[%d] is NULL", r);
     if (n == 0) return 0;
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    const int W = c->group->world_size, me = c->group->rank;
-    const void *const *srcs = (const void *const *)srcs_dev;
-    const uint32_t *amax = NULL;
-    int k = 0;
-    {
-        const int rc = resolve_scale(c, kind, srcs, R, n, scale_exp, st, &amax, &k);
-        if (rc) return rc;
+    struct inccl_scale sc;
+    int rc = resolve_scale(c, kind, srcs, R, n, scale_exp, st, &sc);
+    if (rc) return rc;
+    const enum inccl_route route =
+        inccl_route_of(INCCL_OP_ALLREDUCE, kind, c->group->transport, c->engine, c->group->world_size,
+                       c->force_sharded, c->mesh_rs, n, c->rccl_ar_bytes, c->ll_max_bytes);
+    switch (route) {
+        case INCCL_ROUTE_FUSED:   /* one HBM pass: quant + sum + dequant */
+            return kerr(inccl_k_stream_s(kind, kind, srcs, R, dst, n, sc.k, sc.amax, sc.R, c->out_shift, st));
+        case INCCL_ROUTE_RSAG: return allreduce_rsag(c, kind, srcs, R, dst, n, &sc, chunks, st);
+        case INCCL_ROUTE_AR: return allreduce_via_q32(c, kind, srcs, R, dst, n, 0, n, &sc, st);
+        case INCCL_ROUTE_A2A: return allreduce_a2a(c, srcs, R, (float *)dst, n, &sc, st);
+        default: break;
     }
-    const int scale_R = R * W;
-    if (W == 1 && !c->force_sharded)   /* one fused HBM pass */
-        return kerr(inccl_k_stream_s(kind, kind, srcs, R, dst_dev, n, k, amax, scale_R,
-                                     c->out_shift, st));
-
-    if ((c->engine == INCCL_ENGINE_RCCL && !rccl_small(c, n)) || c->group->transport == INCCL_TRANSPORT_LOCAL) {
-        /* quant + local sum -> reduce-scatter (int32) -> dequantise own shard to
-         * bf16 -> all-gather (bf16), as allreduce_piece with a 2-byte result;
-         * small buckets fall through to the one-all-reduce route at the end */
-        const size_t shard = inccl_shard_elems(n, W), total = shard * (size_t)W;
-        int rc = inccl_ws_claim(c, st);
-        if (rc) return rc;
-        rc = inccl_ensure_dev(&c->d_q32, &c->d_q32_bytes, (total + shard) * sizeof(int32_t));
-        if (rc) return rc;
-        const int in_place = (total == n);
-        if (!in_place) {
-            rc = inccl_ws_claim(c, st);
-            if (rc) return rc;
-            rc = inccl_ensure_dev(&c->d_f32, &c->d_f32_bytes, total * sizeof(uint16_t));
-            if (rc) return rc;
-        }
-        int32_t *qsend = (int32_t *)c->d_q32, *qrecv = qsend + total;
-        rc = kerr(inccl_k_stream(kind, INCCL_KIND_Q32, srcs, R, qsend, n, k, amax, scale_R, st));
-        if (rc) return rc;
-        if (total > n) INCCL_HIP(hipMemsetAsync(qsend + n, 0, (total - n) * sizeof(int32_t), st));
-        rc = inccl_tp_reduce_scatter_q32(c, qsend, qrecv, shard, st);
-        if (rc) return rc;
-        uint16_t *gather = in_place ? dst_dev : (uint16_t *)c->d_f32;
-        const size_t lo = (size_t)me * shard;
-        const void *s1[1] = {qrecv};
-        rc = kerr(inccl_k_stream_s(INCCL_KIND_Q32, kind, s1, 1, gather + lo, shard, k, amax, scale_R,
-                                   c->out_shift, st));
-        if (rc) return rc;
-        rc = inccl_tp_all_gather_bf16(c, gather + lo, gather, shard, st);
-        if (rc) return rc;
-        if (!in_place) INCCL_HIP(hipMemcpyAsync(dst_dev, gather, n * sizeof(uint16_t), hipMemcpyDeviceToDevice, st));
-        return 0;
-    }
-    /* the mesh engines: the persistent kernel with 2-byte sources and results (mesh.c) */
-    if (c->engine == INCCL_ENGINE_MESH && c->group->transport == INCCL_TRANSPORT_RCCL)
-        return inccl_mesh_piece16(c, kind, srcs_dev, R, dst_dev, n, k, amax, scale_R, st);
-    /* the p2p engine: 2-byte result shards gathered over xGMI (p2p.c).  The
-     * route never depends on this rank's dst alignment (every rank must take
-     * it): a dst that is not 4-B aligned gets it into the aligned workspace and
-     * one copy out */
-    if (c->engine == INCCL_ENGINE_P2P && c->group->transport == INCCL_TRANSPORT_RCCL) {
-        if (((uintptr_t)dst_dev & 3u) == 0) return inccl_p2p_piece16(c, kind, srcs_dev, R, dst_dev, n, k, amax, scale_R, st);
-        int rc = inccl_ws_claim(c, st);
+    /* the IPC engines: the ll kernel for small fp32 buckets when the ll engine
+     * was chosen explicitly (ll.c), the one-kernel mesh exchange (mesh.c) or the
+     * host-synchronised p2p exchange (p2p.c).  The p2p engine (and the automatic
+     * fallback to it when RCCL is unavailable) never routes to ll by itself.
+     * The route never depends on this rank's dst alignment (every rank must
+     * take it): a 2-byte dst the p2p gather cannot store to (not 4-B aligned)
+     * gets it into the aligned workspace and one copy out. */
+    void *out = dst;
+    if (route == INCCL_ROUTE_IPC_P2P && kind != INCCL_KIND_F32 && ((uintptr_t)dst & 3u) != 0) {
+        rc = inccl_ws_claim(c, st);
         if (rc) return rc;
         rc = inccl_ensure_dev(&c->d_f32, &c->d_f32_bytes, n * sizeof(uint16_t));
         if (rc) return rc;
-        rc = inccl_p2p_piece16(c, kind, srcs_dev, R, (uint16_t *)c->d_f32, n, k, amax, scale_R, st);
-        if (rc) return rc;
-        INCCL_HIP(hipMemcpyAsync(dst_dev, c->d_f32, n * sizeof(uint16_t), hipMemcpyDeviceToDevice, st));
-        return 0;
+        out = c->d_f32;
     }
-    /* every other engine: its int32 allreduce of the quantised partials (RCCL
-     * all-reduce for "ar" / "a2a", the p2p exchange for the IPC engines) */
-    int rc = inccl_ws_claim(c, st);
+    const int si = stage_open(c, st);
+    if (route == INCCL_ROUTE_IPC_LL) rc = inccl_ll_piece(c, (const float *const *)srcs, R, (float *)dst, n, &sc, 0, 0, st);
+    else if (route == INCCL_ROUTE_IPC_MESH) rc = inccl_mesh_allreduce(c, kind, srcs, R, dst, n, &sc, st);
+    else rc = inccl_p2p_allreduce(c, kind, srcs, R, out, n, &sc, st);
     if (rc) return rc;
-    rc = inccl_ensure_dev(&c->d_q32, &c->d_q32_bytes, n * sizeof(int32_t));
-    if (rc) return rc;
-    int32_t *q = (int32_t *)c->d_q32;
-    rc = kerr(inccl_k_stream(kind, INCCL_KIND_Q32, srcs, R, q, n, k, amax, scale_R, st));
-    if (rc) return rc;
-    rc = inccl_tp_allreduce_q32(c, q, q, n, st);
-    if (rc) return rc;
-    const void *s1[1] = {q};
-    return kerr(inccl_k_stream_s(INCCL_KIND_Q32, kind, s1, 1, dst_dev, n, k, amax, scale_R,
-                                 c->out_shift, st));
+    stage_close(c, si, st, INCCL_STAGE_IPC);
+    if (out != dst) INCCL_HIP(hipMemcpyAsync(dst, out, n * sizeof(uint16_t), hipMemcpyDeviceToDevice, st));
+    return 0;
 }
 
-static int allreduce_16(struct inccl_communicator *c, int kind, const uint16_t *const *srcs_dev, int R,
-                        uint16_t *dst_dev, size_t n, int scale_exp, void *stream)
+static int allreduce_any(struct inccl_communicator *c, int kind, const void *const *srcs, int R, void *dst, size_t n,
+                         int scale_exp, int chunks, void *stream)
 {
-    INCCL_ORDERED(c, stream, allreduce_16_body(c, kind, srcs_dev, R, dst_dev, n, scale_exp, stream));
+    INCCL_ORDERED(c, stream, allreduce_body(c, kind, srcs, R, dst, n, scale_exp, chunks, stream));
+}
+
+int inccl_allreduce_f32(struct inccl_communicator *c, const float *const *srcs_dev, int R, float *dst_dev, size_t n,
+                        int scale_exp, void *stream)
+{
+    return allreduce_any(c, INCCL_KIND_F32, (const void *const *)srcs_dev, R, dst_dev, n, scale_exp, 1, stream);
+}
+
+int inccl_allreduce_f32_pipelined(struct inccl_communicator *c, const float *const *srcs_dev, int R, float *dst_dev,
+                                  size_t n, int scale_exp, int chunks, void *stream)
+{
+    return allreduce_any(c, INCCL_KIND_F32, (const void *const *)srcs_dev, R, dst_dev, n, scale_exp, chunks, stream);
 }
 
 int inccl_allreduce_bf16(struct inccl_communicator *c, const uint16_t *const *srcs_dev, int R, uint16_t *dst_dev,
                          size_t n, int scale_exp, void *stream)
 {
-    return allreduce_16(c, INCCL_KIND_BF16, srcs_dev, R, dst_dev, n, scale_exp, stream);
+    return allreduce_any(c, INCCL_KIND_BF16, (const void *const *)srcs_dev, R, dst_dev, n, scale_exp, 1, stream);
 }
 
 int inccl_allreduce_f16(struct inccl_communicator *c, const uint16_t *const *srcs_dev, int R, uint16_t *dst_dev,
                         size_t n, int scale_exp, void *stream)
 {
-    return allreduce_16(c, INCCL_KIND_F16, srcs_dev, R, dst_dev, n, scale_exp, stream);
+    return allreduce_any(c, INCCL_KIND_F16, (const void *const *)srcs_dev, R, dst_dev, n, scale_exp, 1, stream);
 }
 
 /* Reduce-scatter (include/inccl_amd.h): the allreduce's arithmetic, rank `me`
- * keeping shard me of the result.  kind F32, BF16 or F16. */
+ * keeping shard me (n / W elements, unpadded) of the result.  kind F32, BF16 or
+ * F16. */
 static int reduce_scatter_body(struct inccl_communicator *c, int kind, const void *const *srcs, int R, void *dst,
                                size_t n, int scale_exp, void *stream)
 {
-    static const char *const names[] = {"f32", "", "", "bf16", "f16"};
+    const char *const name = kind_names[kind];
     if (!c || !srcs || R < 1 || R > INCCL_MAX_LOCAL_INPUTS || (!dst && n))
-        return inccl_set_error(INCCL_ERR_ARG, "bad reduce_scatter_%s args", names[kind]);
+        return inccl_set_error(INCCL_ERR_ARG, "bad reduce_scatter_%s args", name);
     for (int r = 0; r < R; ++r)
         if (!srcs[r] && n) return inccl_set_error(INCCL_ERR_ARG, "srcs[%d] is NULL", r);
     const int W = c->group->world_size, me = c->group->rank;
     if (n % (size_t)W)
-        return inccl_set_error(INCCL_ERR_ARG, "reduce_scatter_%s: %zu elements do not split into %d shards",
-                               names[kind], n, W);
+        return inccl_set_error(INCCL_ERR_ARG, "reduce_scatter_%s: %zu elements do not split into %d shards", name, n, W);
     if (n == 0) return 0;
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
     const size_t shard = n / (size_t)W, es = kind == INCCL_KIND_F32 ? 4 : 2;
     for (int r = 0; r < R; ++r) {   /* the one-kernel routes read sources while writing dst */
         const uintptr_t s0 = (uintptr_t)srcs[r], d0 = (uintptr_t)dst;
         if (d0 < s0 + n * es && s0 < d0 + shard * es)
-            return inccl_set_error(INCCL_ERR_ARG, "reduce_scatter_%s: dst overlaps srcs[%d]", names[kind], r);
+            return inccl_set_error(INCCL_ERR_ARG, "reduce_scatter_%s: dst overlaps srcs[%d]", name, r);
     }
-    const uint32_t *amax = NULL;
-    int k = 0;
-    int rc = resolve_scale(c, kind, srcs, R, n, scale_exp, st, &amax, &k);
+    struct inccl_scale sc;
+    int rc = resolve_scale(c, kind, srcs, R, n, scale_exp, st, &sc);
     if (rc) return rc;
-    const int scale_R = R * W;
-    if (W == 1 && !c->force_sharded)   /* one fused HBM pass */
-        return kerr(inccl_k_stream_s(kind, kind, srcs, R, dst, n, k, amax, scale_R, c->out_shift, st));
-    if (c->engine == INCCL_ENGINE_RCCL || c->group->transport == INCCL_TRANSPORT_LOCAL) {
-        /* quant + local sum -> int32 reduce-scatter -> dequantise the shard */
-        rc = inccl_ws_claim(c, st);
-        if (rc) return rc;
-        rc = inccl_ensure_dev(&c->d_q32, &c->d_q32_bytes, (n + shard) * sizeof(int32_t));
-        if (rc) return rc;
-        int32_t *qsend = (int32_t *)c->d_q32, *qrecv = qsend + n;
-        int si = stage_open(c, st);
-        rc = kerr(inccl_k_stream(kind, INCCL_KIND_Q32, srcs, R, qsend, n, k, amax, scale_R, st));
-        if (rc) return rc;
-        stage_close(c, si, st, INCCL_STAGE_QUANT);
-        si = stage_open(c, st);
-        rc = inccl_tp_reduce_scatter_q32(c, qsend, qrecv, shard, st);
-        if (rc) return rc;
-        stage_close(c, si, st, INCCL_STAGE_RS);
-        si = stage_open(c, st);
-        const void *s1[1] = {qrecv};
-        rc = kerr(inccl_k_stream_s(INCCL_KIND_Q32, kind, s1, 1, dst, shard, k, amax, scale_R, c->out_shift, st));
-        stage_close(c, si, st, INCCL_STAGE_DEQUANT);
-        return rc;
-    }
-    const int ipc = c->engine == INCCL_ENGINE_P2P || c->engine == INCCL_ENGINE_LL || c->engine == INCCL_ENGINE_MESH;
-    /* Every route below is chosen from what all ranks share (engine, n, W and
-     * the knobs agreed in agree_knobs), never from this rank's dst alignment:
-     * a dst the vector kernels cannot store to (fp32 not 16-B, 16-bit not 8-B
-     * aligned) gets the same route into an aligned workspace and one copy out. */
-    const int rcclt = c->group->transport == INCCL_TRANSPORT_RCCL;
-    const int mesh_route = c->mesh_rs && c->engine == INCCL_ENGINE_MESH && rcclt && !(shard % 64);
-    const int p2p_route = ipc && rcclt && !(shard & 3);
-    if (mesh_route || p2p_route) {
-        void *out = dst;
-        if (((uintptr_t)dst & (kind == INCCL_KIND_F32 ? 15u : 7u)) != 0) {
+    /* Every route is chosen from what all ranks share (engine, n, W and the
+     * knobs agreed in agree_knobs), never from this rank's dst alignment. */
+    const enum inccl_route route =
+        inccl_route_of(INCCL_OP_REDUCE_SCATTER, kind, c->group->transport, c->engine, W, c->force_sharded, c->mesh_rs,
+                       n, c->rccl_ar_bytes, c->ll_max_bytes);
+    switch (route) {
+        case INCCL_ROUTE_FUSED:   /* one HBM pass */
+            return kerr(inccl_k_stream_s(kind, kind, srcs, R, dst, n, sc.k, sc.amax, sc.R, c->out_shift, st));
+        case INCCL_ROUTE_RS: {    /* quant + local sum -> int32 reduce-scatter -> dequantise the shard */
             rc = inccl_ws_claim(c, st);
             if (rc) return rc;
-            rc = inccl_ensure_dev(&c->d_f32, &c->d_f32_bytes, shard * es);
+            rc = inccl_ensure_dev(&c->d_q32, &c->d_q32_bytes, (n + shard) * sizeof(int32_t));
             if (rc) return rc;
-            out = c->d_f32;
+            int32_t *qsend = (int32_t *)c->d_q32, *qrecv = qsend + n;
+            rc = stage_quant(c, kind, srcs, R, qsend, n, n, &sc, st);
+            if (rc) return rc;
+            const int si = stage_open(c, st);
+            rc = inccl_tp_reduce_scatter_q32(c, qsend, qrecv, shard, st);
+            if (rc) return rc;
+            stage_close(c, si, st, INCCL_STAGE_RS);
+            return stage_dequant(c, kind, qrecv, dst, shard, &sc, st);
         }
-        /* the mesh engines' own route (INCCL_MESH_RS, default on): their one
-         * persistent kernel, the allreduce's instructions with the other ranks'
-         * gathers reduced to their waits (mesh.c; DESIGN.md, "Mesh
-         * reduce-scatter route").  The ll engine's one kernel for a small fp32
-         * bucket: every rank's quads published with a flag, this rank's shard
-         * summed and dequantised.  Otherwise the p2p pull-reduce. */
-        const int si = stage_open(c, st);
-        if (mesh_route)
-            rc = inccl_mesh_reduce_scatter(c, kind, srcs, R, out, n, k, amax, scale_R, st);
-        else if (kind == INCCL_KIND_F32 && c->engine == INCCL_ENGINE_LL && n <= c->ll_max_bytes / sizeof(float))
-            rc = inccl_ll_piece(c, (const float *const *)srcs, R, (float *)out, n, k, amax, scale_R,
-                                (size_t)me * shard, shard, st);
-        else
-            rc = inccl_p2p_reduce_scatter(c, kind, srcs, R, out, n, k, amax, scale_R, st);
-        if (rc) return rc;
-        stage_close(c, si, st, INCCL_STAGE_IPC);
-        if (out == dst) return 0;
-        INCCL_HIP(hipMemcpyAsync(dst, out, shard * es, hipMemcpyDeviceToDevice, st));
-        return 0;
+        case INCCL_ROUTE_AR_SHARD:   /* the engine's int32 allreduce, then the shard dequantised */
+            return allreduce_via_q32(c, kind, srcs, R, dst, n, (size_t)me * shard, shard, &sc, st);
+        default: break;
     }
-    /* every other engine, or a shard the pull-reduce cannot take: the engine's
-     * int32 allreduce, then the shard dequantised */
-    rc = inccl_ws_claim(c, st);
+    /* The IPC routes.  A dst the vector kernels cannot store to (fp32 not 16-B,
+     * 16-bit not 8-B aligned) gets the same route into an aligned workspace and
+     * one copy out. */
+    void *out = dst;
+    if (((uintptr_t)dst & (kind == INCCL_KIND_F32 ? 15u : 7u)) != 0) {
+        rc = inccl_ws_claim(c, st);
+        if (rc) return rc;
+        rc = inccl_ensure_dev(&c->d_f32, &c->d_f32_bytes, shard * es);
+        if (rc) return rc;
+        out = c->d_f32;
+    }
+    /* the mesh engines' own route (INCCL_MESH_RS, default on): their one
+     * persistent kernel, the allreduce's instructions with the other ranks'
+     * gathers reduced to their waits (mesh.c; DESIGN.md, "Mesh reduce-scatter
+     * route").  The ll engine's one kernel for a small fp32 bucket: every
+     * rank's quads published with a flag, this rank's shard summed and
+     * dequantised.  Otherwise the p2p pull-reduce. */
+    const int si = stage_open(c, st);
+    if (route == INCCL_ROUTE_IPC_MESH_RS) rc = inccl_mesh_reduce_scatter(c, kind, srcs, R, out, n, &sc, st);
+    else if (route == INCCL_ROUTE_IPC_LL_RS)
+        rc = inccl_ll_piece(c, (const float *const *)srcs, R, (float *)out, n, &sc, (size_t)me * shard, shard, st);
+    else rc = inccl_p2p_reduce_scatter(c, kind, srcs, R, out, n, &sc, st);
     if (rc) return rc;
-    rc = inccl_ensure_dev(&c->d_q32, &c->d_q32_bytes, n * sizeof(int32_t));
-    if (rc) return rc;
-    int32_t *q = (int32_t *)c->d_q32;
-    rc = kerr(inccl_k_stream(kind, INCCL_KIND_Q32, srcs, R, q, n, k, amax, scale_R, st));
-    if (rc) return rc;
-    rc = inccl_tp_allreduce_q32(c, q, q, n, st);
-    if (rc) return rc;
-    const void *s1[1] = {q + (size_t)me * shard};
-    return kerr(inccl_k_stream_s(INCCL_KIND_Q32, kind, s1, 1, dst, shard, k, amax, scale_R, c->out_shift, st));
+    stage_close(c, si, st, INCCL_STAGE_IPC);
+    if (out != dst) INCCL_HIP(hipMemcpyAsync(dst, out, shard * es, hipMemcpyDeviceToDevice, st));
+    return 0;
 }
 
 static int reduce_scatter_any(struct inccl_communicator *c, int kind, const void *const *srcs, int R, void *dst,

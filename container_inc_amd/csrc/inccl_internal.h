@@ -15,16 +15,8 @@
 #include <hip/hip_runtime_api.h>
 
 #include "inccl_amd.h"
+#include "inccl_route.h"   /* transports, engines, the route of a call */
 
-#define INCCL_TRANSPORT_RCCL 0
-#define INCCL_TRANSPORT_LOCAL 1
-/* communicator-level exchange engine (group transport RCCL only) */
-#define INCCL_ENGINE_RCCL 0
-#define INCCL_ENGINE_P2P 1
-#define INCCL_ENGINE_A2A 2
-#define INCCL_ENGINE_LL 3
-#define INCCL_ENGINE_MESH 4
-#define INCCL_ENGINE_AR 5
 #define INCCL_MAX_HOST_REGIONS 16
 #define INCCL_MESH_REGIONS 4
 /* Largest single allocation exported over HIP IPC (runtime.c).  Importing a
@@ -143,10 +135,9 @@ struct inccl_communicator {
 /* transport operations; all stream-ordered on `st` */
 int inccl_tp_reduce_scatter_q32(struct inccl_communicator *c, const int32_t *send, int32_t *recv, size_t shard,
                                 hipStream_t st);
-int inccl_tp_all_gather_f32(struct inccl_communicator *c, const float *send, float *recv, size_t shard,
-                            hipStream_t st);
-int inccl_tp_all_gather_bf16(struct inccl_communicator *c, const uint16_t *send, uint16_t *recv, size_t shard,
-                             hipStream_t st);
+/* shards of es-byte elements, es 4 or 2 */
+int inccl_tp_all_gather(struct inccl_communicator *c, const void *send, void *recv, size_t shard, size_t es,
+                        hipStream_t st);
 int inccl_tp_allreduce_q32(struct inccl_communicator *c, const int32_t *send, int32_t *recv, size_t n,
                            hipStream_t st);
 int inccl_tp_allreduce_max_u32(struct inccl_communicator *c, uint32_t *buf, size_t n, hipStream_t st);
@@ -157,10 +148,8 @@ int inccl_rccl_comm_init(struct inccl_communicator *c);
 void inccl_rccl_comm_destroy(struct inccl_communicator *c);
 int inccl_rccl_reduce_scatter_q32(struct inccl_communicator *c, const int32_t *send, int32_t *recv, size_t shard,
                                   hipStream_t st);
-int inccl_rccl_all_gather_f32(struct inccl_communicator *c, const float *send, float *recv, size_t shard,
-                              hipStream_t st);
-int inccl_rccl_all_gather_bf16(struct inccl_communicator *c, const uint16_t *send, uint16_t *recv, size_t shard,
-                               hipStream_t st);
+int inccl_rccl_all_gather(struct inccl_communicator *c, const void *send, void *recv, size_t shard, size_t es,
+                          hipStream_t st);
 int inccl_rccl_allreduce_q32(struct inccl_communicator *c, const int32_t *send, int32_t *recv, size_t n,
                              hipStream_t st);
 int inccl_rccl_allreduce_max_u32(struct inccl_communicator *c, uint32_t *buf, size_t n, hipStream_t st);
@@ -168,17 +157,25 @@ int inccl_rccl_allreduce_max_u32(struct inccl_communicator *c, uint32_t *buf, si
 int inccl_rccl_alltoall_q32(struct inccl_communicator *c, const int32_t *send, int32_t *recv, size_t shard,
                             hipStream_t st);
 
-/* p2p engine */
-int inccl_p2p_piece(struct inccl_communicator *c, const float *const *srcs, int R, float *dst, size_t n, int k,
-                    const uint32_t *amax, int scale_R, hipStream_t st);
-/* 2-byte buckets, kind INCCL_KIND_BF16 or INCCL_KIND_F16 */
-int inccl_p2p_piece16(struct inccl_communicator *c, int kind, const uint16_t *const *srcs, int R, uint16_t *dst,
-                      size_t n, int k, const uint32_t *amax, int scale_R, hipStream_t st);
-void inccl_p2p_release(struct inccl_communicator *c);
-/* reduce-scatter of kind F32 / BF16 / F16 buckets over the p2p buffers: n = W *
- * shard, shard % 4 == 0; dst = the dequantised shard `me` (inccl_reduce_scatter_*) */
+/* The scale of one collective call (api.c resolve_scale), as the engines and
+ * the kernels take it: a fixed exponent k, or the device absmax word the
+ * kernels resolve the exponent from (k unused then), and the number of buckets
+ * summed over the whole group. */
+struct inccl_scale {
+    int k;
+    const uint32_t *amax;
+    int R;
+};
+
+/* p2p engine (p2p.c): allreduce and reduce-scatter of kind F32 / BF16 / F16
+ * buckets over its IPC buffers.  The allreduce's 2-byte dst must be 4-byte
+ * aligned; reduce-scatter: n = W * shard, shard % 4 == 0, dst = the dequantised
+ * shard `me` (inccl_reduce_scatter_*) */
+int inccl_p2p_allreduce(struct inccl_communicator *c, int kind, const void *const *srcs, int R, void *dst, size_t n,
+                        const struct inccl_scale *sc, hipStream_t st);
 int inccl_p2p_reduce_scatter(struct inccl_communicator *c, int kind, const void *const *srcs, int R, void *dst,
-                             size_t n, int k, const uint32_t *amax, int scale_R, hipStream_t st);
+                             size_t n, const struct inccl_scale *sc, hipStream_t st);
+void inccl_p2p_release(struct inccl_communicator *c);
 /* int32 allreduce (wrapping sum) over the p2p engine's IPC buffers: the
  * reference API's inccl_allreduce_write on a multi-process group without RCCL */
 int inccl_p2p_allreduce_q32(struct inccl_communicator *c, const int32_t *send, int32_t *recv, size_t n,
@@ -186,18 +183,16 @@ int inccl_p2p_allreduce_q32(struct inccl_communicator *c, const int32_t *send, i
 
 /* ll engine (ll.c): n <= c->ll_max_bytes / 4.  rs_n > 0: reduce-scatter, dst =
  * elements [rs_lo, rs_lo + rs_n) of the result (both multiples of 4) */
-int inccl_ll_piece(struct inccl_communicator *c, const float *const *srcs, int R, float *dst, size_t n, int k,
-                   const uint32_t *amax, int scale_R, size_t rs_lo, size_t rs_n, hipStream_t st);
+int inccl_ll_piece(struct inccl_communicator *c, const float *const *srcs, int R, float *dst, size_t n,
+                   const struct inccl_scale *sc, size_t rs_lo, size_t rs_n, hipStream_t st);
 void inccl_ll_release(struct inccl_communicator *c);
 uint64_t inccl_wait_ticks(struct inccl_group *g);   /* bound of an in-kernel wait */
 
-/* mesh engine (mesh.c) */
-int inccl_mesh_piece(struct inccl_communicator *c, const float *const *srcs, int R, float *dst, size_t n, int k,
-                     const uint32_t *amax, int scale_R, hipStream_t st);
-int inccl_mesh_piece16(struct inccl_communicator *c, int kind, const uint16_t *const *srcs, int R, uint16_t *dst,
-                       size_t n, int k, const uint32_t *amax, int scale_R, hipStream_t st);
+/* mesh engine (mesh.c), kind F32 / BF16 / F16 */
+int inccl_mesh_allreduce(struct inccl_communicator *c, int kind, const void *const *srcs, int R, void *dst, size_t n,
+                         const struct inccl_scale *sc, hipStream_t st);
 int inccl_mesh_reduce_scatter(struct inccl_communicator *c, int kind, const void *const *srcs, int R, void *dst,
-                              size_t n, int k, const uint32_t *amax, int scale_R, hipStream_t st);
+                              size_t n, const struct inccl_scale *sc, hipStream_t st);
 void inccl_mesh_release(struct inccl_communicator *c);
 
 /* local transport */
@@ -205,8 +200,6 @@ struct inccl_local_hub *inccl_hub_attach(const char *name, int world_size);
 void inccl_hub_detach(struct inccl_local_hub *hub);
 int inccl_local_reduce_scatter_q32(struct inccl_communicator *c, const int32_t *send, int32_t *recv, size_t shard,
                                    hipStream_t st);
-int inccl_local_all_gather_f32(struct inccl_communicator *c, const float *send, float *recv, size_t shard,
-                               hipStream_t st);
 int inccl_local_allreduce_q32(struct inccl_communicator *c, const int32_t *send, int32_t *recv, size_t n,
                               hipStream_t st);
 int inccl_local_allreduce_max_u32(struct inccl_communicator *c, uint32_t *buf, size_t n, hipStream_t st);

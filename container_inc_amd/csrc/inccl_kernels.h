@@ -18,30 +18,23 @@ int inccl_k_stream(int in_kind, int out_kind, const void *const *srcs, int R, vo
 /* the same with the dequantise scaled by 2^-out_shift (inccl_comm_set_average) */
 int inccl_k_stream_s(int in_kind, int out_kind, const void *const *srcs, int R, void *dst, size_t n, int scale_exp,
                      const uint32_t *amax_bits_dev, int scale_R, int out_shift, void *stream);
-int inccl_k_absmax(const float *const *srcs, int R, size_t n, uint32_t *amax_bits_dev, int zero_first, void *stream);
-int inccl_k_absmax_bf16(const uint16_t *const *srcs, int R, size_t n, uint32_t *amax_bits_dev, int zero_first,
-                        void *stream);
-int inccl_k_absmax_f16(const uint16_t *const *srcs, int R, size_t n, uint32_t *amax_bits_dev, int zero_first,
-                        void *stream);
+/* absmax word of R buckets of kind F32 / BF16 / F16 (include/inccl_amd.h inccl_absmax_*) */
+int inccl_k_absmax(int kind, const void *const *srcs, int R, size_t n, uint32_t *amax_bits_dev, int zero_first,
+                   void *stream);
 int inccl_k_checksum(const int32_t *q, size_t n, uint64_t index_base, uint32_t *out_dev, int zero_first,
                      void *stream);
 void inccl_k_set_tuning(int grid_cap, int nt_loads);
-/* p2p engine kernels reading peer memory with system-coherent loads (inccl_peer.hip):
- * dst[i] = dequant(sum_j peers[j][i]), n % 4 == 0, 16-B aligned; and
- * dst[off[j] .. off[j]+cnt[j]) = src[j][0 .. cnt[j]) for j < nseg, one launch */
-int inccl_k_peer_reduce(const void *const *peers, int W, float *dst, size_t n, int scale_exp,
+/* p2p engine kernels reading peer memory with system-coherent loads (inccl_peer.hip).
+ * The pull-reduce, n % 4 == 0, by out_kind:
+ *   F32          dst[i] = dequant(sum_j peers[j][i]), dst 16-B aligned
+ *   BF16 / F16   the same narrowed round to nearest even, dst 8-B aligned
+ *   Q32          dst[i] = sum_j peers[j][i] (int32, wrapping; the scale is unused), dst 16-B aligned */
+int inccl_k_peer_reduce(int out_kind, const void *const *peers, int W, void *dst, size_t n, int scale_exp,
                         const uint32_t *amax_bits_dev, int scale_R, int out_shift, void *stream);
-int inccl_k_peer_gather(const void *const *src, const int64_t *off, const int64_t *cnt, int nseg, void *dst,
+/* dst[off[j] .. off[j]+cnt[j]) = src[j][0 .. cnt[j]) for j < nseg in one launch; es-byte elements, es 4 or
+ * 2 (counts and even offsets in elements; dst 4-B aligned) */
+int inccl_k_peer_gather(int es, const void *const *src, const int64_t *off, const int64_t *cnt, int nseg, void *dst,
                         void *stream);
-/* the pull-reduce with 2-byte results: dst[i] = narrow(dequant(sum_j peers[j][i])), narrow = bf16 (kind
- * INCCL_KIND_BF16) or fp16 (INCCL_KIND_F16) round to nearest even, n % 4 == 0, dst 8-B aligned */
-int inccl_k_peer_reduce16(int kind, const void *const *peers, int W, uint16_t *dst, size_t n, int scale_exp,
-                          const uint32_t *amax_bits_dev, int scale_R, int out_shift, void *stream);
-/* the same gather for 2-byte elements (counts and even offsets in elements; dst 4-B aligned) */
-int inccl_k_peer_gather16(const void *const *src, const int64_t *off, const int64_t *cnt, int nseg, void *dst,
-                          void *stream);
-/* dst[i] = sum_j peers[j][i] (int32, wrapping), n % 4 == 0, 16-B aligned */
-int inccl_k_peer_sum_q32(const void *const *peers, int W, int32_t *dst, size_t n, void *stream);
 
 /* the one-kernel small-bucket allreduce (inccl_ll.hip) */
 #define INCCL_LL_MAX_BLOCKS 256   /* workgroups per call = flags per rank in a signal array */

@@ -442,24 +442,16 @@ int inccl_k_stream(int in_kind, int out_kind, const void* const* srcs, int R, vo
     return inccl_k_stream_s(in_kind, out_kind, srcs, R, dst, n, scale_exp, amax_bits_dev, scale_R, 0, stream);
 }
 
-int inccl_k_absmax(const float* const* srcs, int R, size_t n, uint32_t* amax_bits_dev, int zero_first, void* stream)
+int inccl_k_absmax(int kind, const void* const* srcs, int R, size_t n, uint32_t* amax_bits_dev, int zero_first,
+                   void* stream)
 {
-    return launch_absmax<F32>(reinterpret_cast<const void* const*>(srcs), R, n, amax_bits_dev, zero_first,
-                              (hipStream_t)stream);
-}
-
-int inccl_k_absmax_bf16(const uint16_t* const* srcs, int R, size_t n, uint32_t* amax_bits_dev, int zero_first,
-                        void* stream)
-{
-    return launch_absmax<BF16>(reinterpret_cast<const void* const*>(srcs), R, n, amax_bits_dev, zero_first,
-                               (hipStream_t)stream);
-}
-
-int inccl_k_absmax_f16(const uint16_t* const* srcs, int R, size_t n, uint32_t* amax_bits_dev, int zero_first,
-                       void* stream)
-{
-    return launch_absmax<F16>(reinterpret_cast<const void* const*>(srcs), R, n, amax_bits_dev, zero_first,
-                              (hipStream_t)stream);
+    hipStream_t st = (hipStream_t)stream;
+    switch (kind) {
+        case F32: return launch_absmax<F32>(srcs, R, n, amax_bits_dev, zero_first, st);
+        case BF16: return launch_absmax<BF16>(srcs, R, n, amax_bits_dev, zero_first, st);
+        case F16: return launch_absmax<F16>(srcs, R, n, amax_bits_dev, zero_first, st);
+        default: return INCCL_ERR_ARG;
+    }
 }
 
 int inccl_k_checksum(const int32_t* q, size_t n, uint64_t index_base, uint32_t* out_dev, int zero_first, void* stream)

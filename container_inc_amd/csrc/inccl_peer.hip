@@ -186,38 +186,14 @@ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 
 }  // namespace
 
-extern "C" int inccl_k_peer_reduce(const void* const* peers, int W, float* dst, size_t n, int scale_exp,
+// The pull-reduce for every result kind: F32 (dequantised), BF16 / F16 (dequantised
+// and narrowed; dst 8-B aligned) or Q32 (the int32 sum itself, no float arithmetic).
+extern "C" int inccl_k_peer_reduce(int out_kind, const void* const* peers, int W, void* dst, size_t n, int scale_exp,
                                    const uint32_t* amax_bits_dev, int scale_R, int out_shift, void* stream)
 {
-    if (W < 1 || W > kMaxR || dst == nullptr || (n & 3) != 0 || !aligned16(dst)) return INCCL_ERR_ARG;
-    if (n == 0) return 0;
-    SrcPtrs s = {};
-    for (int j = 0; j < W; ++j) {
-        if (peers[j] == nullptr || !aligned16(peers[j])) return INCCL_ERR_ARG;
-        s.p[j] = peers[j];
-    }
-    Scale sc{scale_exp, amax_bits_dev, scale_R > 0 ? scale_R : W, out_shift};
-    const int64_t n4 = (int64_t)(n >> 2);
-    hipStream_t st = (hipStream_t)stream;
-    hipError_t e;
-    switch (W) {
-        case 1: e = launch_reduce_R<1>(s, dst, n4, sc, st); break;
-        case 2: e = launch_reduce_R<2>(s, dst, n4, sc, st); break;
-        case 3: e = launch_reduce_R<3>(s, dst, n4, sc, st); break;
-        case 4: e = launch_reduce_R<4>(s, dst, n4, sc, st); break;
-        case 5: e = launch_reduce_R<5>(s, dst, n4, sc, st); break;
-        case 6: e = launch_reduce_R<6>(s, dst, n4, sc, st); break;
-        case 7: e = launch_reduce_R<7>(s, dst, n4, sc, st); break;
-        default: e = launch_reduce_R<8>(s, dst, n4, sc, st); break;
-    }
-    return e == hipSuccess ? 0 : (int)e;
-}
-
-extern "C" int inccl_k_peer_reduce16(int kind, const void* const* peers, int W, uint16_t* dst, size_t n,
-                                     int scale_exp, const uint32_t* amax_bits_dev, int scale_R, int out_shift,
-                                     void* stream)
-{
-    if ((kind != BF16 && kind != F16) || W < 1 || W > kMaxR || dst == nullptr || (n & 3) != 0 || (reinterpret_cast<uintptr_t>(dst) & 7u) != 0)
+    const bool half = out_kind == BF16 || out_kind == F16;
+    if ((!half && out_kind != F32 && out_kind != Q32) || W < 1 || W > kMaxR || dst == nullptr || (n & 3) != 0 ||
+        (reinterpret_cast<uintptr_t>(dst) & (half ? 7u : 15u)) != 0)
         return INCCL_ERR_ARG;
     if (n == 0) return 0;
     SrcPtrs s = {};
@@ -228,96 +204,57 @@ extern "C" int inccl_k_peer_reduce16(int kind, const void* const* peers, int W, 
     Scale sc{scale_exp, amax_bits_dev, scale_R > 0 ? scale_R : W, out_shift};
     const int64_t n4 = (int64_t)(n >> 2);
     hipStream_t st = (hipStream_t)stream;
-    switch (W) {
+    float* d = reinterpret_cast<float*>(dst);   // 32-bit words; no float arithmetic without DEQ
+    hipError_t e = hipSuccess;
+#define INCCL_BY_W(X) \
+    switch (W) { case 1: X(1) break; case 2: X(2) break; case 3: X(3) break; case 4: X(4) break; \
+                 case 5: X(5) break; case 6: X(6) break; case 7: X(7) break; default: X(8) break; }
+#define INCCL_PR32(WW) e = launch_reduce_R<WW>(s, d, n4, sc, st);
 #define INCCL_PR16(WW)                                                                                                \
-    case WW: {                                                                                                         \
+    {                                                                                                                  \
         constexpr int B = Geometry<WW>::BLOCK;                                                                         \
         const dim3 g((unsigned)((n4 + B - 1) / B));                                                                    \
-        if (kind == F16)                                                                                               \
-            hipLaunchKernelGGL((k_peer_reduce16<WW, B, F16>), g, dim3(B), 0, st, s, dst, n4, sc);                      \
+        uint16_t* d16 = reinterpret_cast<uint16_t*>(dst);                                                              \
+        if (out_kind == F16)                                                                                           \
+            hipLaunchKernelGGL((k_peer_reduce16<WW, B, F16>), g, dim3(B), 0, st, s, d16, n4, sc);                      \
         else                                                                                                           \
-            hipLaunchKernelGGL((k_peer_reduce16<WW, B, BF16>), g, dim3(B), 0, st, s, dst, n4, sc);                     \
-        break;                                                                                                         \
+            hipLaunchKernelGGL((k_peer_reduce16<WW, B, BF16>), g, dim3(B), 0, st, s, d16, n4, sc);                     \
+        e = hipGetLastError();                                                                                         \
     }
-        INCCL_PR16(1) INCCL_PR16(2) INCCL_PR16(3) INCCL_PR16(4) INCCL_PR16(5) INCCL_PR16(6) INCCL_PR16(7)
-        default: INCCL_PR16(8)
+#define INCCL_PRQ(WW) e = launch_reduce_R<WW, false>(s, d, n4, sc, st);
+    if (out_kind == F32) INCCL_BY_W(INCCL_PR32)
+    else if (half) INCCL_BY_W(INCCL_PR16)
+    else INCCL_BY_W(INCCL_PRQ)
+#undef INCCL_PRQ
 #undef INCCL_PR16
-    }
-    const hipError_t e = hipGetLastError();
+#undef INCCL_PR32
+#undef INCCL_BY_W
     return e == hipSuccess ? 0 : (int)e;
 }
 
-extern "C" int inccl_k_peer_sum_q32(const void* const* peers, int W, int32_t* dst, size_t n, void* stream)
+// dst[off[j] .. off[j]+cnt[j]) = src[j][0 .. cnt[j]) of es-byte elements, es 4 or 2.
+// 2-byte elements (bf16 / fp16 result shards) move as whole 4-byte words, plus the
+// odd last element of a segment: dst must be 4-byte aligned and every offset even.
+extern "C" int inccl_k_peer_gather(int es, const void* const* src, const int64_t* off, const int64_t* cnt, int nseg,
+                                   void* dst, void* stream)
 {
-    if (W < 1 || W > kMaxR || dst == nullptr || (n & 3) != 0 || !aligned16(dst)) return INCCL_ERR_ARG;
-    if (n == 0) return 0;
-    SrcPtrs s = {};
-    for (int j = 0; j < W; ++j) {
-        if (peers[j] == nullptr || !aligned16(peers[j])) return INCCL_ERR_ARG;
-        s.p[j] = peers[j];
-    }
-    const Scale sc{0, nullptr, W};
-    const int64_t n4 = (int64_t)(n >> 2);
-    float* d = reinterpret_cast<float*>(dst);   // 32-bit words; no float arithmetic without DEQ
-    hipStream_t st = (hipStream_t)stream;
-    hipError_t e;
-    switch (W) {
-        case 1: e = launch_reduce_R<1, false>(s, d, n4, sc, st); break;
-        case 2: e = launch_reduce_R<2, false>(s, d, n4, sc, st); break;
-        case 3: e = launch_reduce_R<3, false>(s, d, n4, sc, st); break;
-        case 4: e = launch_reduce_R<4, false>(s, d, n4, sc, st); break;
-        case 5: e = launch_reduce_R<5, false>(s, d, n4, sc, st); break;
-        case 6: e = launch_reduce_R<6, false>(s, d, n4, sc, st); break;
-        case 7: e = launch_reduce_R<7, false>(s, d, n4, sc, st); break;
-        default: e = launch_reduce_R<8, false>(s, d, n4, sc, st); break;
-    }
-    return e == hipSuccess ? 0 : (int)e;
-}
-
-static int launch_gather(Segs& s, int64_t maxc, void* dst, void* stream);
-
-extern "C" int inccl_k_peer_gather(const void* const* src, const int64_t* off, const int64_t* cnt, int nseg, void* dst,
-                                   void* stream)
-{
-    if (nseg < 1 || nseg > kMaxR || dst == nullptr) return INCCL_ERR_ARG;
-    Segs s = {};
-    s.nseg = nseg;
-    int64_t maxc = 0;
-    for (int j = 0; j < nseg; ++j) {
-        if ((src[j] == nullptr && cnt[j] > 0) || cnt[j] < 0 || !aligned16(src[j])) return INCCL_ERR_ARG;
-        s.src[j] = src[j];
-        s.off[j] = off[j];
-        s.cnt[j] = cnt[j];
-        maxc = cnt[j] > maxc ? cnt[j] : maxc;
-    }
-    return launch_gather(s, maxc, dst, stream);
-}
-
-// 2-byte elements (bf16 result shards): whole 4-byte words, plus the odd last
-// element of a segment.  dst must be 4-byte aligned and every offset even.
-extern "C" int inccl_k_peer_gather16(const void* const* src, const int64_t* off, const int64_t* cnt, int nseg,
-                                     void* dst, void* stream)
-{
-    if (nseg < 1 || nseg > kMaxR || dst == nullptr || (reinterpret_cast<uintptr_t>(dst) & 3u) != 0)
+    const bool half = es == 2;
+    if ((es != 4 && !half) || nseg < 1 || nseg > kMaxR || dst == nullptr ||
+        (half && (reinterpret_cast<uintptr_t>(dst) & 3u) != 0))
         return INCCL_ERR_ARG;
     Segs s = {};
     s.nseg = nseg;
     int64_t maxc = 0;
     for (int j = 0; j < nseg; ++j) {
-        if ((src[j] == nullptr && cnt[j] > 0) || cnt[j] < 0 || (off[j] & 1) || !aligned16(src[j])) return INCCL_ERR_ARG;
+        if ((src[j] == nullptr && cnt[j] > 0) || cnt[j] < 0 || (half && (off[j] & 1)) || !aligned16(src[j]))
+            return INCCL_ERR_ARG;
         s.src[j] = src[j];
-        s.off[j] = off[j] >> 1;
-        s.cnt[j] = cnt[j] >> 1;
-        s.tail16[j] = (int)(cnt[j] & 1);
+        s.off[j] = half ? off[j] >> 1 : off[j];
+        s.cnt[j] = half ? cnt[j] >> 1 : cnt[j];
+        s.tail16[j] = half ? (int)(cnt[j] & 1) : 0;
         const int64_t c = s.cnt[j] + s.tail16[j];
         maxc = c > maxc ? c : maxc;
     }
-    return launch_gather(s, maxc, dst, stream);
-}
-
-static int launch_gather(Segs& s, int64_t maxc, void* dst, void* stream)
-{
-    const int nseg = s.nseg;
     if (maxc == 0) return 0;
     const int64_t tile = (int64_t)kGatherBlock * kGatherU * 4;
     int64_t gx = (maxc + tile - 1) / tile;

@@ -107,8 +107,8 @@ uint64_t inccl_wait_ticks(struct inccl_group *g)
     return (uint64_t)(ms * (double)khz);
 }
 
-int inccl_ll_piece(struct inccl_communicator *c, const float *const *srcs, int R, float *dst, size_t n, int k,
-                   const uint32_t *amax, int scale_R, size_t rs_lo, size_t rs_n, hipStream_t st)
+int inccl_ll_piece(struct inccl_communicator *c, const float *const *srcs, int R, float *dst, size_t n,
+                   const struct inccl_scale *sc, size_t rs_lo, size_t rs_n, hipStream_t st)
 {
     const int W = c->group->world_size, me = c->group->rank;
     if (!c->ll_buf) {   /* the collective setup cannot run inside a graph capture */
@@ -140,9 +140,9 @@ int inccl_ll_piece(struct inccl_communicator *c, const float *const *srcs, int R
     l.W = W;
     l.me = me;
     l.timeout_ticks = c->ll_timeout_ticks;
-    l.scale_exp = k;
-    l.amax_bits = amax;
-    l.scale_R = scale_R;
+    l.scale_exp = sc->k;
+    l.amax_bits = sc->amax;
+    l.scale_R = sc->R;
     l.out_shift = c->out_shift;
     l.rs_lo = rs_lo;
     l.rs_n = rs_n;

@@ -263,7 +263,7 @@ static void mesh_flag_census(struct inccl_communicator *c, uint32_t e, uint32_t 
 }
 
 static int mesh_piece(struct inccl_communicator *c, int kind16, const void *const *srcs, int R, void *dst, size_t n,
-                      int k, const uint32_t *amax, int scale_R, int rs, hipStream_t st)
+                      const struct inccl_scale *sc, int rs, hipStream_t st)
 {
     const int W = c->group->world_size, me = c->group->rank;
     const size_t shard = inccl_shard_elems(n, W);
@@ -344,9 +344,9 @@ static int mesh_piece(struct inccl_communicator *c, int kind16, const void *cons
     l.W = W;
     l.me = me;
     l.timeout_ticks = c->mesh_timeout_ticks;
-    l.scale_exp = k;
-    l.amax_bits = amax;
-    l.scale_R = scale_R;
+    l.scale_exp = sc->k;
+    l.amax_bits = sc->amax;
+    l.scale_R = sc->R;
     l.out_shift = c->out_shift;
     const size_t es = kind16 ? sizeof(uint16_t) : sizeof(float);   /* source and result element bytes */
     l.src_bytes = n * es;
@@ -367,10 +367,15 @@ static int mesh_piece(struct inccl_communicator *c, int kind16, const void *cons
     return 0;
 }
 
-int inccl_mesh_piece(struct inccl_communicator *c, const float *const *srcs, int R, float *dst, size_t n, int k,
-                     const uint32_t *amax, int scale_R, hipStream_t st)
+/* the allreduce of kind F32, BF16 or F16 buckets; the 2-byte kinds run the same
+ * kernel with 2-byte sources, int32 partials and a 2-byte result, so the xGMI
+ * bytes are 4 + 2 per element instead of 4 + 4 */
+int inccl_mesh_allreduce(struct inccl_communicator *c, int kind, const void *const *srcs, int R, void *dst, size_t n,
+                         const struct inccl_scale *sc, hipStream_t st)
 {
-    return mesh_piece(c, 0, (const void *const *)srcs, R, dst, n, k, amax, scale_R, 0, st);
+    if (kind != INCCL_KIND_F32 && kind != INCCL_KIND_BF16 && kind != INCCL_KIND_F16)
+        return inccl_set_error(INCCL_ERR_ARG, "mesh: bad kind %d", kind);
+    return mesh_piece(c, kind == INCCL_KIND_F32 ? 0 : kind, srcs, R, dst, n, sc, 0, st);
 }
 
 /* reduce-scatter (inccl_reduce_scatter_*): the same kernel and the same
@@ -379,16 +384,7 @@ int inccl_mesh_piece(struct inccl_communicator *c, const float *const *srcs, int
  * into dst (its n / W elements, n % (64 W) == 0); kind INCCL_KIND_F32, BF16 or
  * F16 */
 int inccl_mesh_reduce_scatter(struct inccl_communicator *c, int kind, const void *const *srcs, int R, void *dst,
-                              size_t n, int k, const uint32_t *amax, int scale_R, hipStream_t st)
+                              size_t n, const struct inccl_scale *sc, hipStream_t st)
 {
-    return mesh_piece(c, kind == INCCL_KIND_F32 ? 0 : kind, srcs, R, dst, n, k, amax, scale_R, 1, st);
-}
-
-/* bf16 / fp16 buckets: the same kernel with 2-byte sources, int32 partials and a
- * 2-byte result, so the xGMI bytes are 4 + 2 per element instead of 4 + 4 */
-int inccl_mesh_piece16(struct inccl_communicator *c, int kind, const uint16_t *const *srcs, int R, uint16_t *dst,
-                       size_t n, int k, const uint32_t *amax, int scale_R, hipStream_t st)
-{
-    if (kind != INCCL_KIND_BF16 && kind != INCCL_KIND_F16) return inccl_set_error(INCCL_ERR_ARG, "mesh: bad kind %d", kind);
-    return mesh_piece(c, kind, (const void *const *)srcs, R, dst, n, k, amax, scale_R, 0, st);
+    return mesh_piece(c, kind == INCCL_KIND_F32 ? 0 : kind, srcs, R, dst, n, sc, 1, st);
 }

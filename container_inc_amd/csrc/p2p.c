@@ -182,161 +182,91 @@ static int sync_and_barrier(struct inccl_communicator *c, hipStream_t st)
     return inccl_group_barrier(c->group);
 }
 
-int inccl_p2p_piece(struct inccl_communicator *c, const float *const *srcs, int R, float *dst, size_t n, int k,
-                    const uint32_t *amax, int scale_R, hipStream_t st)
+/* The one exchange every p2p call is (steps 1-5 of the header comment):
+ *   fill    in_kind F32 / BF16 / F16: quant + local sum of the R buckets -> part;
+ *           in_kind Q32: srcs[0] copied into part (the int32 allreduce)
+ *   reduce  shard `me` pulled from every peer and summed; out_kind F32 / BF16 /
+ *           F16 dequantises (and narrows: 2 bytes per element over xGMI instead
+ *           of 4), Q32 leaves the int32 sum (the reference's switch add,
+ *           nts.c:361-363, and nothing else)
+ *   gather  != 0: the allreduce -- shards padded (inccl_shard_elems), the reduce
+ *           lands in res at me * shard and every rank's shard is gathered into
+ *           dst (2-byte kinds: dst 4-byte aligned);
+ *           0: reduce-scatter -- n = W * shard, shard % 4 == 0, the reduce lands
+ *           straight in dst; the closing barrier keeps every rank from rewriting
+ *           its part (the next call's fill) while a peer still reads it. */
+static int p2p_exchange(struct inccl_communicator *c, int in_kind, const void *const *srcs, int R, int out_kind,
+                        void *dst, size_t n, const struct inccl_scale *sc, int gather, hipStream_t st)
 {
     const int W = c->group->world_size, me = c->group->rank;
     if (W > INCCL_MAX_LOCAL_INPUTS) return inccl_set_error(INCCL_ERR_ARG, "p2p engine supports up to %d GPUs",
                                                           INCCL_MAX_LOCAL_INPUTS);
-    const size_t shard = inccl_shard_elems(n, W), total = shard * (size_t)W;
+    if (n == 0) return 0;
+    const int half = out_kind == INCCL_KIND_BF16 || out_kind == INCCL_KIND_F16;
+    const size_t es = half ? sizeof(uint16_t) : sizeof(float);   /* result element bytes */
+    const char *what = !gather ? "" : out_kind == INCCL_KIND_Q32 ? "int32 " : half ? "16-bit " : "";
+    const size_t shard = gather ? inccl_shard_elems(n, W) : n / (size_t)W, total = shard * (size_t)W;
+    if (!gather && (total != n || (shard & 3))) return inccl_set_error(INCCL_ERR_ARG, "p2p reduce-scatter: bad shard");
     int rc = p2p_ensure(c, total);
     if (rc) return rc;
     /* the previous call's gather may still be reading the peers' result shards,
      * which the peers rewrite once this call's first barrier has passed: order
      * it before that barrier's host sync when the caller switches streams */
     if (c->p2p_last_stream && c->p2p_last_stream != st) INCCL_HIP(hipStreamWaitEvent(st, c->ev[8], 0));
-    /* 1. local quantise + sum */
-    rc = inccl_k_stream(INCCL_KIND_F32, INCCL_KIND_Q32, (const void *const *)srcs, R, c->p2p_part, n, k, amax,
-                        scale_R, st);
-    if (rc) return inccl_set_error(INCCL_ERR_HIP, "p2p quant+sum launch failed (%d)", rc);
+    /* 1. fill part */
+    if (in_kind == INCCL_KIND_Q32) {
+        INCCL_HIP(hipMemcpyAsync(c->p2p_part, srcs[0], n * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+    } else {
+        rc = inccl_k_stream(in_kind, INCCL_KIND_Q32, srcs, R, c->p2p_part, n, sc->k, sc->amax, sc->R, st);
+        if (rc) return inccl_set_error(INCCL_ERR_HIP, "p2p %squant+sum launch failed (%d)",
+                                       gather ? what : "reduce-scatter ", rc);
+    }
     if (total > n) INCCL_HIP(hipMemsetAsync(c->p2p_part + n, 0, (total - n) * sizeof(int32_t), st));
     rc = sync_and_barrier(c, st);
     if (rc) return rc;
     /* 3. pull shard `me` from every peer, sum, dequantise */
     const void *peer[INCCL_MAX_LOCAL_INPUTS];
     for (int j = 0; j < W; ++j) peer[j] = c->p2p_peer_part[j] + (size_t)me * shard;
-    rc = inccl_k_peer_reduce(peer, W, c->p2p_res + (size_t)me * shard, shard, k, amax, scale_R, c->out_shift, st);
-    if (rc) return inccl_set_error(INCCL_ERR_HIP, "p2p reduce-scatter launch failed (%d)", rc);
+    rc = inccl_k_peer_reduce(out_kind, peer, W, gather ? (void *)((char *)c->p2p_res + (size_t)me * shard * es) : dst,
+                             shard, sc->k, sc->amax, sc->R, out_kind == INCCL_KIND_Q32 ? 0 : c->out_shift, st);
+    if (rc) return inccl_set_error(INCCL_ERR_HIP, "p2p %sreduce-scatter launch failed (%d)", what, rc);
     rc = sync_and_barrier(c, st);
     if (rc) return rc;
-    /* 5. gather every shard into dst (ragged last shard clamped to n) */
-    const void *src[INCCL_MAX_LOCAL_INPUTS];
-    int64_t off[INCCL_MAX_LOCAL_INPUTS], cnt[INCCL_MAX_LOCAL_INPUTS];
-    for (int j = 0; j < W; ++j) {
-        const size_t lo = (size_t)j * shard;
-        src[j] = c->p2p_peer_res[j] + lo;
-        off[j] = (int64_t)lo;
-        cnt[j] = lo >= n ? 0 : (int64_t)((n - lo) < shard ? (n - lo) : shard);
+    if (gather) {
+        /* 5. gather every shard into dst (ragged last shard clamped to n) */
+        const void *src[INCCL_MAX_LOCAL_INPUTS];
+        int64_t off[INCCL_MAX_LOCAL_INPUTS], cnt[INCCL_MAX_LOCAL_INPUTS];
+        for (int j = 0; j < W; ++j) {
+            const size_t lo = (size_t)j * shard;
+            src[j] = (const char *)c->p2p_peer_res[j] + lo * es;
+            off[j] = (int64_t)lo;
+            cnt[j] = lo >= n ? 0 : (int64_t)((n - lo) < shard ? (n - lo) : shard);
+        }
+        rc = inccl_k_peer_gather((int)es, src, off, cnt, W, dst, st);
+        if (rc) return inccl_set_error(INCCL_ERR_HIP, "p2p %sgather launch failed (%d)", what, rc);
     }
-    rc = inccl_k_peer_gather(src, off, cnt, W, dst, st);
-    if (rc) return inccl_set_error(INCCL_ERR_HIP, "p2p gather launch failed (%d)", rc);
     INCCL_HIP(hipEventRecord(c->ev[8], st));
     c->p2p_last_stream = st;
     return 0;
 }
 
-/* bfloat16 / float16 buckets (kind) over the same buffers and barriers: quant +
- * local sum of the 2-byte buckets -> part; barrier; shard `me` pulled from every
- * peer, summed, dequantised and narrowed in one kernel into res (2-byte elements
- * at me * shard); barrier; every rank's 2-byte result shard gathered -- 2 bytes
- * per element over xGMI instead of the int32 allreduce's 4.  dst must be 4-byte
- * aligned. */
-int inccl_p2p_piece16(struct inccl_communicator *c, int kind, const uint16_t *const *srcs, int R, uint16_t *dst,
-                      size_t n, int k, const uint32_t *amax, int scale_R, hipStream_t st)
+int inccl_p2p_allreduce(struct inccl_communicator *c, int kind, const void *const *srcs, int R, void *dst, size_t n,
+                        const struct inccl_scale *sc, hipStream_t st)
 {
-    const int W = c->group->world_size, me = c->group->rank;
-    if (W > INCCL_MAX_LOCAL_INPUTS) return inccl_set_error(INCCL_ERR_ARG, "p2p engine supports up to %d GPUs",
-                                                          INCCL_MAX_LOCAL_INPUTS);
-    const size_t shard = inccl_shard_elems(n, W), total = shard * (size_t)W;
-    int rc = p2p_ensure(c, total);
-    if (rc) return rc;
-    if (c->p2p_last_stream && c->p2p_last_stream != st) INCCL_HIP(hipStreamWaitEvent(st, c->ev[8], 0));
-    rc = inccl_k_stream(kind, INCCL_KIND_Q32, (const void *const *)srcs, R, c->p2p_part, n, k, amax, scale_R, st);
-    if (rc) return inccl_set_error(INCCL_ERR_HIP, "p2p 16-bit quant+sum launch failed (%d)", rc);
-    if (total > n) INCCL_HIP(hipMemsetAsync(c->p2p_part + n, 0, (total - n) * sizeof(int32_t), st));
-    rc = sync_and_barrier(c, st);
-    if (rc) return rc;
-    const void *peer[INCCL_MAX_LOCAL_INPUTS];
-    for (int j = 0; j < W; ++j) peer[j] = c->p2p_peer_part[j] + (size_t)me * shard;
-    rc = inccl_k_peer_reduce16(kind, peer, W, (uint16_t *)c->p2p_res + (size_t)me * shard, shard, k, amax, scale_R,
-                               c->out_shift, st);
-    if (rc) return inccl_set_error(INCCL_ERR_HIP, "p2p 16-bit reduce-scatter launch failed (%d)", rc);
-    rc = sync_and_barrier(c, st);
-    if (rc) return rc;
-    const void *src[INCCL_MAX_LOCAL_INPUTS];
-    int64_t off[INCCL_MAX_LOCAL_INPUTS], cnt[INCCL_MAX_LOCAL_INPUTS];
-    for (int j = 0; j < W; ++j) {
-        const size_t lo = (size_t)j * shard;
-        src[j] = (const uint16_t *)c->p2p_peer_res[j] + lo;
-        off[j] = (int64_t)lo;
-        cnt[j] = lo >= n ? 0 : (int64_t)((n - lo) < shard ? (n - lo) : shard);
-    }
-    rc = inccl_k_peer_gather16(src, off, cnt, W, dst, st);
-    if (rc) return inccl_set_error(INCCL_ERR_HIP, "p2p 16-bit gather launch failed (%d)", rc);
-    INCCL_HIP(hipEventRecord(c->ev[8], st));
-    c->p2p_last_stream = st;
-    return 0;
+    return p2p_exchange(c, kind, srcs, R, kind, dst, n, sc, 1, st);
 }
 
-/* Reduce-scatter over the same buffers: quant + local sum -> part; barrier;
- * shard `me` pulled from every peer, summed and dequantised (narrowed for the
- * 2-byte kinds) straight into dst; barrier, so that no rank rewrites its part
- * (the next call's quantise) while a peer still reads it.  n = W * shard,
- * shard % 4 == 0. */
 int inccl_p2p_reduce_scatter(struct inccl_communicator *c, int kind, const void *const *srcs, int R, void *dst,
-                             size_t n, int k, const uint32_t *amax, int scale_R, hipStream_t st)
+                             size_t n, const struct inccl_scale *sc, hipStream_t st)
 {
-    const int W = c->group->world_size, me = c->group->rank;
-    if (W > INCCL_MAX_LOCAL_INPUTS) return inccl_set_error(INCCL_ERR_ARG, "p2p engine supports up to %d GPUs",
-                                                          INCCL_MAX_LOCAL_INPUTS);
-    const size_t shard = n / (size_t)W;
-    if (shard * (size_t)W != n || (shard & 3)) return inccl_set_error(INCCL_ERR_ARG, "p2p reduce-scatter: bad shard");
-    int rc = p2p_ensure(c, n);
-    if (rc) return rc;
-    if (c->p2p_last_stream && c->p2p_last_stream != st) INCCL_HIP(hipStreamWaitEvent(st, c->ev[8], 0));
-    rc = inccl_k_stream(kind, INCCL_KIND_Q32, srcs, R, c->p2p_part, n, k, amax, scale_R, st);
-    if (rc) return inccl_set_error(INCCL_ERR_HIP, "p2p reduce-scatter quant+sum launch failed (%d)", rc);
-    rc = sync_and_barrier(c, st);
-    if (rc) return rc;
-    const void *peer[INCCL_MAX_LOCAL_INPUTS];
-    for (int j = 0; j < W; ++j) peer[j] = c->p2p_peer_part[j] + (size_t)me * shard;
-    rc = kind == INCCL_KIND_F32
-             ? inccl_k_peer_reduce(peer, W, (float *)dst, shard, k, amax, scale_R, c->out_shift, st)
-             : inccl_k_peer_reduce16(kind, peer, W, (uint16_t *)dst, shard, k, amax, scale_R, c->out_shift, st);
-    if (rc) return inccl_set_error(INCCL_ERR_HIP, "p2p reduce-scatter launch failed (%d)", rc);
-    rc = sync_and_barrier(c, st);
-    if (rc) return rc;
-    INCCL_HIP(hipEventRecord(c->ev[8], st));
-    c->p2p_last_stream = st;
-    return 0;
+    return p2p_exchange(c, kind, srcs, R, kind, dst, n, sc, 0, st);
 }
 
-/* The int32 allreduce over the same buffers and barriers as inccl_p2p_piece,
- * with the sum left in int32 (the reference's switch add, nts.c:361-363, and
- * nothing else): copy in -> barrier -> pull + sum shard `me` from every peer ->
- * barrier -> gather every shard.  send may alias recv. */
+/* send may alias recv */
 int inccl_p2p_allreduce_q32(struct inccl_communicator *c, const int32_t *send, int32_t *recv, size_t n,
                             hipStream_t st)
 {
-    const int W = c->group->world_size, me = c->group->rank;
-    if (W > INCCL_MAX_LOCAL_INPUTS) return inccl_set_error(INCCL_ERR_ARG, "p2p engine supports up to %d GPUs",
-                                                          INCCL_MAX_LOCAL_INPUTS);
-    if (n == 0) return 0;
-    const size_t shard = inccl_shard_elems(n, W), total = shard * (size_t)W;
-    int rc = p2p_ensure(c, total);
-    if (rc) return rc;
-    if (c->p2p_last_stream && c->p2p_last_stream != st) INCCL_HIP(hipStreamWaitEvent(st, c->ev[8], 0));
-    INCCL_HIP(hipMemcpyAsync(c->p2p_part, send, n * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-    if (total > n) INCCL_HIP(hipMemsetAsync(c->p2p_part + n, 0, (total - n) * sizeof(int32_t), st));
-    rc = sync_and_barrier(c, st);
-    if (rc) return rc;
-    const void *peer[INCCL_MAX_LOCAL_INPUTS];
-    for (int j = 0; j < W; ++j) peer[j] = c->p2p_peer_part[j] + (size_t)me * shard;
-    rc = inccl_k_peer_sum_q32(peer, W, (int32_t *)(c->p2p_res + (size_t)me * shard), shard, st);
-    if (rc) return inccl_set_error(INCCL_ERR_HIP, "p2p int32 reduce-scatter launch failed (%d)", rc);
-    rc = sync_and_barrier(c, st);
-    if (rc) return rc;
-    const void *src[INCCL_MAX_LOCAL_INPUTS];
-    int64_t off[INCCL_MAX_LOCAL_INPUTS], cnt[INCCL_MAX_LOCAL_INPUTS];
-    for (int j = 0; j < W; ++j) {
-        const size_t lo = (size_t)j * shard;
-        src[j] = c->p2p_peer_res[j] + lo;
-        off[j] = (int64_t)lo;
-        cnt[j] = lo >= n ? 0 : (int64_t)((n - lo) < shard ? (n - lo) : shard);
-    }
-    rc = inccl_k_peer_gather(src, off, cnt, W, recv, st);
-    if (rc) return inccl_set_error(INCCL_ERR_HIP, "p2p int32 gather launch failed (%d)", rc);
-    INCCL_HIP(hipEventRecord(c->ev[8], st));
-    c->p2p_last_stream = st;
-    return 0;
+    static const struct inccl_scale none = {0, NULL, 0};
+    const void *s1[1] = {send};
+    return p2p_exchange(c, INCCL_KIND_Q32, s1, 1, INCCL_KIND_Q32, recv, n, &none, 1, st);
 }

@@ -87,16 +87,12 @@ int inccl_rccl_reduce_scatter_q32(struct inccl_communicator *c, const int32_t *s
                       "ncclReduceScatter");
 }
 
-int inccl_rccl_all_gather_f32(struct inccl_communicator *c, const float *send, float *recv, size_t shard,
-                              hipStream_t st)
+/* an all-gather copies bytes: es-byte elements travel as ncclFloat32 (4) or ncclBfloat16 (2) */
+int inccl_rccl_all_gather(struct inccl_communicator *c, const void *send, void *recv, size_t shard, size_t es,
+                          hipStream_t st)
 {
-    return nccl_call(c, ncclAllGather(send, recv, shard, ncclFloat32, (ncclComm_t)c->nccl, st), "ncclAllGather");
-}
-
-int inccl_rccl_all_gather_bf16(struct inccl_communicator *c, const uint16_t *send, uint16_t *recv, size_t shard,
-                               hipStream_t st)
-{
-    return nccl_call(c, ncclAllGather(send, recv, shard, ncclBfloat16, (ncclComm_t)c->nccl, st), "ncclAllGather(bf16)");
+    return nccl_call(c, ncclAllGather(send, recv, shard, es == 4 ? ncclFloat32 : ncclBfloat16, (ncclComm_t)c->nccl, st),
+                     es == 4 ? "ncclAllGather" : "ncclAllGather(bf16)");
 }
 
 int inccl_rccl_allreduce_q32(struct inccl_communicator *c, const int32_t *send, int32_t *recv, size_t n,
@@ -247,12 +243,6 @@ static int local_all_gather(struct inccl_communicator *c, const void *send, void
     return rc ? rc : rc2;
 }
 
-int inccl_local_all_gather_f32(struct inccl_communicator *c, const float *send, float *recv, size_t shard,
-                               hipStream_t st)
-{
-    return local_all_gather(c, send, recv, shard, sizeof(float), st);
-}
-
 int inccl_local_allreduce_q32(struct inccl_communicator *c, const int32_t *send, int32_t *recv, size_t n,
                               hipStream_t st)
 {
@@ -333,30 +323,17 @@ int inccl_tp_reduce_scatter_q32(struct inccl_communicator *c, const int32_t *sen
     return inccl_rccl_reduce_scatter_q32(c, send, recv, shard, st);
 }
 
-int inccl_tp_all_gather_f32(struct inccl_communicator *c, const float *send, float *recv, size_t shard,
-                            hipStream_t st)
+int inccl_tp_all_gather(struct inccl_communicator *c, const void *send, void *recv, size_t shard, size_t es,
+                        hipStream_t st)
 {
-    if (is_local(c)) return inccl_local_all_gather_f32(c, send, recv, shard, st);
+    if (is_local(c)) return local_all_gather(c, send, recv, shard, es, st);
     int rc = ensure_rccl(c);
     if (rc) return rc;
     if (!c->nccl) {
-        if (send != recv) INCCL_HIP(hipMemcpyAsync(recv, send, shard * 4, hipMemcpyDeviceToDevice, st));
+        if (send != recv) INCCL_HIP(hipMemcpyAsync(recv, send, shard * es, hipMemcpyDeviceToDevice, st));
         return 0;
     }
-    return inccl_rccl_all_gather_f32(c, send, recv, shard, st);
-}
-
-int inccl_tp_all_gather_bf16(struct inccl_communicator *c, const uint16_t *send, uint16_t *recv, size_t shard,
-                             hipStream_t st)
-{
-    if (is_local(c)) return local_all_gather(c, send, recv, shard, sizeof(uint16_t), st);
-    int rc = ensure_rccl(c);
-    if (rc) return rc;
-    if (!c->nccl) {
-        if (send != recv) INCCL_HIP(hipMemcpyAsync(recv, send, shard * 2, hipMemcpyDeviceToDevice, st));
-        return 0;
-    }
-    return inccl_rccl_all_gather_bf16(c, send, recv, shard, st);
+    return inccl_rccl_all_gather(c, send, recv, shard, es, st);
 }
 
 int inccl_tp_allreduce_q32(struct inccl_communicator *c, const int32_t *send, int32_t *recv, size_t n,
@@ -364,8 +341,7 @@ int inccl_tp_allreduce_q32(struct inccl_communicator *c, const int32_t *send, in
 {
     if (is_local(c)) return inccl_local_allreduce_q32(c, send, recv, n, st);
     /* the IPC engines carry the int32 allreduce without RCCL */
-    if ((c->engine == INCCL_ENGINE_P2P || c->engine == INCCL_ENGINE_LL || c->engine == INCCL_ENGINE_MESH) &&
-        c->group->world_size > 1)
+    if (inccl_engine_is_ipc(c->engine) && c->group->world_size > 1)
         return inccl_p2p_allreduce_q32(c, send, recv, n, st);
     int rc = ensure_rccl(c);
     if (rc) return rc;
@@ -379,7 +355,7 @@ int inccl_tp_allreduce_q32(struct inccl_communicator *c, const int32_t *send, in
 int inccl_tp_allreduce_max_u32(struct inccl_communicator *c, uint32_t *buf, size_t n, hipStream_t st)
 {
     if (is_local(c)) return inccl_local_allreduce_max_u32(c, buf, n, st);
-    if ((c->engine == INCCL_ENGINE_P2P || c->engine == INCCL_ENGINE_LL || c->engine == INCCL_ENGINE_MESH) && n == 1)
+    if (inccl_engine_is_ipc(c->engine) && n == 1)
         return host_allreduce_max_u32(c, buf, st);
     int rc = ensure_rccl(c);
     if (rc) return rc;

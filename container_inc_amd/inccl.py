@@ -202,62 +202,52 @@ def reduce_f16(srcs, scale_exp: int, out=None, stream=None):
     return stream_op(KIND_F16, KIND_F16, list(srcs), out, scale_exp, scale_R=len(srcs), stream=stream)
 
 
-def absmax_f16(srcs, stream=None) -> float:
+def _absmax(srcs, dtype=None, word=None, flags: int = 1, stream=None):
+    """The device absmax word (fp32 bits of max |x|) over R buckets, as an int32
+    tensor; dtype None: the buckets' own format (fp32 / bf16 / fp16)."""
     torch = _torch()
+    dt = srcs[0].dtype if dtype is None else dtype
+    fn = {torch.float32: "inccl_absmax_f32", torch.bfloat16: "inccl_absmax_bf16",
+          torch.float16: "inccl_absmax_f16"}[dt]
     n = srcs[0].numel()
-    ptrs = [_dev_ptr(s, torch.float16, f"srcs[{i}]", n) for i, s in enumerate(srcs)]
-    word = torch.zeros(4, dtype=torch.int32, device=srcs[0].device)
-    rc = load().inccl_absmax_f16(_ptr_array(ptrs), len(ptrs), n, _dev_ptr(word, torch.int32, "word", 1), 1,
-                                 _stream_handle(stream))
-    check(rc, "inccl_absmax_f16")
-    bits = int(word[0].item()) & 0xFFFFFFFF
-    return float(np.array([bits], np.uint32).view(np.float32)[0])
+    ptrs = [_dev_ptr(s, dt, f"srcs[{i}]", n) for i, s in enumerate(srcs)]
+    if word is None:
+        word = torch.zeros(4, dtype=torch.int32, device=srcs[0].device)
+    rc = getattr(load(), fn)(_ptr_array(ptrs), len(ptrs), n, _dev_ptr(word, torch.int32, "word", 1), flags,
+                             _stream_handle(stream))
+    check(rc, fn)
+    return word
+
+
+def _word_bits(word) -> int:
+    return int(word[0].item()) & 0xFFFFFFFF
+
+
+def _word_float(word) -> float:
+    return float(np.array([_word_bits(word)], np.uint32).view(np.float32)[0])
+
+
+def absmax_f16(srcs, stream=None) -> float:
+    return _word_float(_absmax(srcs, _torch().float16, stream=stream))
 
 
 def absmax_bf16(srcs, stream=None) -> float:
-    torch = _torch()
-    n = srcs[0].numel()
-    ptrs = [_dev_ptr(s, torch.bfloat16, f"srcs[{i}]", n) for i, s in enumerate(srcs)]
-    word = torch.zeros(4, dtype=torch.int32, device=srcs[0].device)
-    rc = load().inccl_absmax_bf16(_ptr_array(ptrs), len(ptrs), n, _dev_ptr(word, torch.int32, "word", 1), 1,
-                                  _stream_handle(stream))
-    check(rc, "inccl_absmax_bf16")
-    bits = int(word[0].item()) & 0xFFFFFFFF
-    return float(np.array([bits], np.uint32).view(np.float32)[0])
+    return _word_float(_absmax(srcs, _torch().bfloat16, stream=stream))
 
 
 def absmax_word(srcs, word=None, stream=None):
     """Device absmax over R buckets; returns the int32 word tensor holding float bits."""
-    torch = _torch()
-    n = srcs[0].numel()
-    ptrs = [_dev_ptr(s, torch.float32, f"srcs[{i}]", n) for i, s in enumerate(srcs)]
-    if word is None:
-        word = torch.zeros(4, dtype=torch.int32, device=srcs[0].device)
-    rc = load().inccl_absmax_f32(_ptr_array(ptrs), len(ptrs), n, _dev_ptr(word, torch.int32, "word", 1), 1,
-                                 _stream_handle(stream))
-    check(rc, "inccl_absmax_f32")
-    return word
+    return _absmax(srcs, _torch().float32, word=word, stream=stream)
 
 
 def absmax_bits(srcs, nonfinite_flag: bool = False, stream=None) -> int:
     """The raw absmax word (fp32 bits of max |x|) of fp32 / bf16 / fp16 buckets;
     nonfinite_flag: INCCL_ABSMAX_FLAG_NONFINITE (a NaN or +-Inf sets bit 31)."""
-    torch = _torch()
-    n = srcs[0].numel()
-    fn, dt = {torch.float32: ("inccl_absmax_f32", torch.float32), torch.bfloat16: ("inccl_absmax_bf16", torch.bfloat16),
-              torch.float16: ("inccl_absmax_f16", torch.float16)}[srcs[0].dtype]
-    ptrs = [_dev_ptr(s, dt, f"srcs[{i}]", n) for i, s in enumerate(srcs)]
-    word = torch.zeros(4, dtype=torch.int32, device=srcs[0].device)
-    rc = getattr(load(), fn)(_ptr_array(ptrs), len(ptrs), n, _dev_ptr(word, torch.int32, "word", 1),
-                             1 | (ABSMAX_FLAG_NONFINITE if nonfinite_flag else 0), _stream_handle(stream))
-    check(rc, fn)
-    return int(word[0].item()) & 0xFFFFFFFF
+    return _word_bits(_absmax(srcs, flags=1 | (ABSMAX_FLAG_NONFINITE if nonfinite_flag else 0), stream=stream))
 
 
 def absmax(srcs, stream=None) -> float:
-    w = absmax_word(srcs, stream=stream)
-    bits = int(w[0].item()) & 0xFFFFFFFF
-    return float(np.array([bits], np.uint32).view(np.float32)[0])
+    return _word_float(absmax_word(srcs, stream=stream))
 
 
 def reduce_f32_auto(srcs, out=None, word=None, stream=None):
@@ -432,20 +422,28 @@ class Communicator:
         check(load().inccl_host_deregister(self.handle, p), "inccl_host_deregister")
 
     # -- additive device API --
-    def allreduce_f32(self, srcs, out=None, scale_exp: int = 25, chunks: int = 1, stream=None):
+    def _allreduce(self, fmt: str, srcs, out, scale_exp, stream, chunks=None):
+        """allreduce_f32 / _bf16 / _f16: fmt names the format; chunks (fp32 only)
+        selects the pipelined entry point."""
         torch = _torch()
+        dt = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}[fmt]
         srcs = list(srcs)
         if not 1 <= len(srcs) <= MAX_LOCAL_INPUTS:
             raise ValueError(f"1..{MAX_LOCAL_INPUTS} local buckets, got {len(srcs)}")
         n = srcs[0].numel()
-        ptrs = [_dev_ptr(s, torch.float32, f"srcs[{i}]", n) for i, s in enumerate(srcs)]
+        ptrs = [_dev_ptr(s, dt, f"srcs[{i}]", n) for i, s in enumerate(srcs)]
         if out is None:
-            out = torch.empty(n, dtype=torch.float32, device=srcs[0].device)
-        optr = _dev_ptr(out, torch.float32, "out", n)
-        rc = load().inccl_allreduce_f32_pipelined(self.handle, _ptr_array(ptrs), len(ptrs), optr, n,
-                                                  _check_scale(scale_exp), int(chunks), _stream_handle(stream))
-        check(rc, "inccl_allreduce_f32")
+            out = torch.empty(n, dtype=dt, device=srcs[0].device)
+        args = [self.handle, _ptr_array(ptrs), len(ptrs), _dev_ptr(out, dt, "out", n), n, _check_scale(scale_exp)]
+        if chunks is None:
+            rc = getattr(load(), f"inccl_allreduce_{fmt}")(*args, _stream_handle(stream))
+        else:
+            rc = load().inccl_allreduce_f32_pipelined(*args, int(chunks), _stream_handle(stream))
+        check(rc, f"inccl_allreduce_{fmt}")
         return out
+
+    def allreduce_f32(self, srcs, out=None, scale_exp: int = 25, chunks: int = 1, stream=None):
+        return self._allreduce("f32", srcs, out, scale_exp, stream, chunks=chunks)
 
     def prepare_allreduce_f32(self, srcs, out=None, scale_exp: int = 25, chunks: int = 1, stream=None) -> PreparedOp:
         """``allreduce_f32`` with its arguments bound once: ``op()`` runs it."""
@@ -461,19 +459,7 @@ class Communicator:
 
     def allreduce_f16(self, srcs, out=None, scale_exp: int = SCALE_AUTO, stream=None):
         """IEEE fp16 buckets (include/inccl_amd.h inccl_allreduce_f16)."""
-        torch = _torch()
-        srcs = list(srcs)
-        if not 1 <= len(srcs) <= MAX_LOCAL_INPUTS:
-            raise ValueError(f"1..{MAX_LOCAL_INPUTS} local buckets, got {len(srcs)}")
-        n = srcs[0].numel()
-        ptrs = [_dev_ptr(s, torch.float16, f"srcs[{i}]", n) for i, s in enumerate(srcs)]
-        if out is None:
-            out = torch.empty(n, dtype=torch.float16, device=srcs[0].device)
-        optr = _dev_ptr(out, torch.float16, "out", n)
-        rc = load().inccl_allreduce_f16(self.handle, _ptr_array(ptrs), len(ptrs), optr, n, _check_scale(scale_exp),
-                                        _stream_handle(stream))
-        check(rc, "inccl_allreduce_f16")
-        return out
+        return self._allreduce("f16", srcs, out, scale_exp, stream)
 
     def reduce_scatter(self, srcs, out=None, scale_exp: int = SCALE_AUTO, stream=None):
         """Reduce-scatter of fp32 / bf16 / fp16 buckets (include/inccl_amd.h
@@ -502,19 +488,7 @@ class Communicator:
 
     def allreduce_bf16(self, srcs, out=None, scale_exp: int = SCALE_AUTO, stream=None):
         """bfloat16 buckets (include/inccl_amd.h inccl_allreduce_bf16)."""
-        torch = _torch()
-        srcs = list(srcs)
-        if not 1 <= len(srcs) <= MAX_LOCAL_INPUTS:
-            raise ValueError(f"1..{MAX_LOCAL_INPUTS} local buckets, got {len(srcs)}")
-        n = srcs[0].numel()
-        ptrs = [_dev_ptr(s, torch.bfloat16, f"srcs[{i}]", n) for i, s in enumerate(srcs)]
-        if out is None:
-            out = torch.empty(n, dtype=torch.bfloat16, device=srcs[0].device)
-        optr = _dev_ptr(out, torch.bfloat16, "out", n)
-        rc = load().inccl_allreduce_bf16(self.handle, _ptr_array(ptrs), len(ptrs), optr, n, _check_scale(scale_exp),
-                                         _stream_handle(stream))
-        check(rc, "inccl_allreduce_bf16")
-        return out
+        return self._allreduce("bf16", srcs, out, scale_exp, stream)
 
     def allreduce_q32(self, src, out=None, stream=None):
         torch = _torch()

@@ -238,7 +238,10 @@ int inccl_comm_set_nonfinite(struct inccl_communicator *comm, int mode);
  * to the last one's end; sum(us) - wall is the time the stages overlapped (the
  * pipelined rccl path quantises chunk i+1 beside chunk i's collectives).
  * Returns the number of stages recorded (0: none, e.g. timing off or a captured
- * call), negative on error. */
+ * call), negative on error.  Every format records alike: an fp32, bf16 or fp16
+ * bucket on the same route runs the same host code, so a 2-byte allreduce (which
+ * once recorded nothing) reports the stages of its route as an fp32 one does;
+ * so does a reduce-scatter that goes through the engine's int32 allreduce. */
 #define INCCL_STAGE_QUANT 0    /* quantise + local sum (+ the tail memset) */
 #define INCCL_STAGE_RS 1       /* int32 reduce-scatter (ncclReduceScatter, or the in-process one) */
 #define INCCL_STAGE_DEQUANT 2  /* dequantise the own shard */

@@ -133,7 +133,11 @@ def run(rank, world, port, q, mode, iters=2, dtype="f32", as_view=False, engine=
         from container_inc_amd import ddp, inccl
         from oracle import oracle as O
 
-        dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{port}", rank=rank, world_size=world)
+        # gloo's waits bounded like the library's own (INCCL_BOOT_TIMEOUT): by default a
+        # rank whose peer is gone waits 30 minutes for it
+        import datetime
+        dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{port}", rank=rank, world_size=world,
+                                timeout=datetime.timedelta(seconds=120))
         if mode == "gpu":
             torch.cuda.set_device(0)
             dev = torch.device("cuda", 0)

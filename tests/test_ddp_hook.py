@@ -34,9 +34,17 @@ def run_world(world, mode, timeout, dtype="f32", as_view=False, engine="p2p", po
           for r in range(world)]
     for p in ps:
         p.start()
-    res = dict(q.get(timeout=timeout) for _ in range(world))
-    for p in ps:
-        p.join(timeout=60)
+    try:
+        res = dict(q.get(timeout=timeout) for _ in range(world))
+    finally:
+        # a rank that never reported must not outlive the test: left waiting for a
+        # peer that is gone, it holds the GPU and this process's exit (which joins
+        # its children)
+        for p in ps:
+            p.join(timeout=60)
+            if p.is_alive():
+                p.kill()
+                p.join()
     return res
 
 

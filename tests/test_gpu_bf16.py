@@ -91,10 +91,14 @@ def test_allreduce_bf16_dst_aliases_src(gpu, orc):
     grp.destroy()
 
 
-@pytest.mark.parametrize("world,R,n,k", [(2, 2, 1 << 20, 25), (3, 1, 100_001, "auto"), (4, 2, (1 << 18) + 3, 22),
-                                         (8, 1, 65_536, "auto")])
-def test_allreduce_bf16_local(gpu, orc, world, R, n, k):
-    """reduce-scatter (int32) -> dequantise own shard to bf16 -> all-gather (bf16)."""
+@pytest.mark.parametrize("world,R,n,k,engine",
+                         [(2, 2, 1 << 20, 25, None), (3, 1, 100_001, "auto", None), (4, 2, (1 << 18) + 3, 22, None),
+                          (8, 1, 65_536, "auto", None), (2, 2, 4099, 22, "ar")],
+                         ids=["2-2-1048576-25", "3-1-100001-auto", "4-2-262147-22", "8-1-65536-auto", "2-2-4099-22-ar"])
+def test_allreduce_bf16_local(gpu, orc, world, R, n, k, engine):
+    """reduce-scatter (int32) -> dequantise own shard to bf16 -> all-gather (bf16);
+    an in-process "ar" communicator takes the same route for 2-byte buckets
+    (tests/c/route_table.c pins the route; here the result)."""
     import torch
     from container_inc_amd import inccl
     rng = np.random.default_rng(world * 10 + R)
@@ -104,11 +108,13 @@ def test_allreduce_bf16_local(gpu, orc, world, R, n, k):
     want = orc.reduce_bf16(every, kk)
     dev_in = [[_dev(h, gpu) for h in per] for per in hs]
     torch.cuda.synchronize()
-    hub = f"bf16-{world}-{R}-{n}"
+    hub = f"bf16-{world}-{R}-{n}-{engine}"
 
     def rank(r):
         grp = inccl.inccl_group_create_local(world, r, hub)
         comm = inccl.inccl_communicator_create(grp, 0)
+        if engine:
+            comm.set_engine(engine)
         out = torch.empty(n, dtype=torch.bfloat16, device=gpu)
         res = []
         for _ in range(2):   # buffer reuse
@@ -128,7 +134,9 @@ def test_allreduce_bf16_local(gpu, orc, world, R, n, k):
 
 def test_allreduce_bf16_rccl_world1(gpu, orc, monkeypatch):
     """RCCL transport at world 1 through the sharded path: ncclReduceScatter and
-    the bf16 ncclAllGather are real RCCL calls on a one-rank communicator."""
+    the bf16 ncclAllGather are real RCCL calls on a one-rank communicator; "ar",
+    and "a2a" (no 16-bit route of its own), take one ncclAllReduce of the int32
+    partials, as the rccl engine does for a bucket within INCCL_RCCL_AR_BYTES."""
     import torch
     from container_inc_amd import inccl
     monkeypatch.setenv("INCCL_FORCE_RCCL", "1")
@@ -143,13 +151,23 @@ def test_allreduce_bf16_rccl_world1(gpu, orc, monkeypatch):
     out = torch.empty(n, dtype=torch.bfloat16, device=gpu)
     srcs = [_dev(h, gpu) for h in hs]
     torch.cuda.synchronize()
-    for eng in ("rccl", "ar"):
+    for eng in ("rccl", "ar", "a2a"):
         comm.set_engine(eng)
         out.fill_(float("nan"))
         torch.cuda.synchronize()
         comm.allreduce_bf16(srcs, out=out, scale_exp=24, stream=comm.stream)
         torch.cuda.synchronize()
         np.testing.assert_array_equal(_host(out), orc.reduce_bf16(hs, 24), err_msg=eng)
+    # the rccl engine's small-bucket route: one ncclAllReduce of the int32 partials
+    monkeypatch.setenv("INCCL_RCCL_AR_BYTES", str(n * 8))
+    small = inccl.inccl_communicator_create(grp, 0)
+    assert small.engine == "rccl"
+    out.fill_(float("nan"))
+    torch.cuda.synchronize()
+    small.allreduce_bf16(srcs, out=out, scale_exp=24, stream=small.stream)
+    torch.cuda.synchronize()
+    np.testing.assert_array_equal(_host(out), orc.reduce_bf16(hs, 24), err_msg="rccl, small bucket")
+    small.destroy()
     comm.destroy()
     grp.destroy()
 
@@ -217,12 +235,13 @@ def _p2p_rank(rank, world, port, q, engine="p2p"):
 
 
 @pytest.mark.parametrize("world,engine", [(2, "p2p"), (3, "p2p"), (8, "p2p"), (2, "mesh"), (3, "mesh"), (4, "meshw"),
-                                          (8, "mesh")])
+                                          (8, "mesh"), (2, "ll")])
 def test_allreduce_bf16_p2p_multiprocess(gpu, world, engine):
     """The IPC engines' bf16 paths: p2p (bf16 result shards gathered, odd element
     counts through the gather's 2-byte tail; a 2-byte-aligned dst takes the int32
     allreduce) and mesh / meshw (the persistent kernel with bf16 sources and
-    results, any dst alignment), each also in place."""
+    results, any dst alignment), each also in place; ll has no 2-byte route and
+    takes the int32 allreduce for every dst."""
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()

@@ -120,7 +120,9 @@ def test_allreduce_f16_local(gpu, orc, world, R, n, k):
 
 def test_allreduce_f16_rccl_world1(gpu, orc, monkeypatch):
     """RCCL transport at world 1 through the sharded path: ncclReduceScatter and
-    the 2-byte ncclAllGather are real RCCL calls on a one-rank communicator."""
+    the 2-byte ncclAllGather are real RCCL calls on a one-rank communicator; "ar",
+    and "a2a" (no 16-bit route of its own), take one ncclAllReduce of the int32
+    partials, as the rccl engine does for a bucket within INCCL_RCCL_AR_BYTES."""
     import torch
     from container_inc_amd import inccl
     monkeypatch.setenv("INCCL_FORCE_RCCL", "1")
@@ -142,6 +144,16 @@ def test_allreduce_f16_rccl_world1(gpu, orc, monkeypatch):
         comm.allreduce_f16(srcs, out=out, scale_exp=24, stream=comm.stream)
         torch.cuda.synchronize()
         np.testing.assert_array_equal(_host(out), orc.reduce_f16(hs, 24), err_msg=eng)
+    # the rccl engine's small-bucket route: one ncclAllReduce of the int32 partials
+    monkeypatch.setenv("INCCL_RCCL_AR_BYTES", str(n * 8))
+    small = inccl.inccl_communicator_create(grp, 0)
+    assert small.engine == "rccl"
+    out.fill_(float("nan"))
+    torch.cuda.synchronize()
+    small.allreduce_f16(srcs, out=out, scale_exp=24, stream=small.stream)
+    torch.cuda.synchronize()
+    np.testing.assert_array_equal(_host(out), orc.reduce_f16(hs, 24), err_msg="rccl, small bucket")
+    small.destroy()
     comm.destroy()
     grp.destroy()
 

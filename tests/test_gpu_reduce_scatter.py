@@ -197,7 +197,7 @@ def _ipc_rank(rank, world, port, q, engine, mesh_rs=None, misalign=False):
                                 comm.ipc_mem_kind("p2p")
                     else:
                         comm.ipc_mem_kind("p2p")    # INCCL_MESH_RS=0: the p2p pull-reduce
-        if misalign:   # the 16-bit allreduce: a dst that is not 4-B aligned on odd ranks (api.c allreduce_16_body)
+        if misalign:   # the 16-bit allreduce: a dst that is not 4-B aligned on odd ranks (api.c allreduce_body)
             for kind in ("bf16", "f16"):
                 n = world * 4096 + 2
                 hs = [_bucket(np.random.default_rng(77 + r), n, kind) for r in range(world)]
