@@ -42,6 +42,9 @@ SIGNATURES = {
     "inccl_sum_dequant_q32": (_I, [_P, _I, _P, _SZ, _I, _I, _P]),
     "inccl_stream_op": (_I, [_I, _I, _P, _I, _P, _SZ, _I, _P, _I, _P]),
     "inccl_absmax_f32": (_I, [_P, _I, _SZ, _P, _I, _P]),
+    "inccl_block_absmax_f32": (_I, [_P, _I, _SZ, _P, _I, _P]),
+    "inccl_reduce_f32_block": (_I, [_P, _I, _P, _SZ, _P, _I, _P]),
+    "inccl_stream_op_block": (_I, [_I, _I, _P, _I, _P, _SZ, _P, _SZ, _I, _P]),
     "inccl_checksum_q32": (_I, [_P, _SZ, _U64, _P, _I, _P]),
     "inccl_choose_scale": (_I, [_F, _I]),
     "inccl_choose_scale_word": (_I, [_U32, _I, _P]),

@@ -88,6 +88,12 @@ int inccl_mem_kind(const void *p)
 /* ------------------------------------------------------------------ */
 /* stateless device API                                                 */
 /* ------------------------------------------------------------------ */
+/* INCCL_SCALE_BLOCK handed to something that has one exponent per call */
+static int block_refused(const char *what)
+{
+    return inccl_set_error(INCCL_ERR_ARG, "INCCL_SCALE_BLOCK (per-block auto scaling) is not available for %s", what);
+}
+
 static int kerr(int rc)
 {
     if (rc == 0) return 0;
@@ -99,7 +105,32 @@ int inccl_stream_op(int in_kind, int out_kind, const void *const *srcs_dev, int 
                     int scale_exp, const uint32_t *amax_bits_dev, int scale_R, void *stream)
 {
     if (!srcs_dev) return inccl_set_error(INCCL_ERR_ARG, "srcs is NULL");
+    if (scale_exp == INCCL_SCALE_BLOCK && !amax_bits_dev) return block_refused("a fixed-exponent stream op");
     return kerr(inccl_k_stream(in_kind, out_kind, srcs_dev, R, dst_dev, n, scale_exp, amax_bits_dev, scale_R, stream));
+}
+
+/* ---- per-block auto scaling, stateless (include/inccl_amd.h) ---- */
+int inccl_block_absmax_f32(const float *const *srcs_dev, int R, size_t n, uint32_t *words_dev, int flags, void *stream)
+{
+    if (!srcs_dev) return inccl_set_error(INCCL_ERR_ARG, "srcs is NULL");
+    return kerr(inccl_k_block_absmax((const void *const *)srcs_dev, R, n, words_dev, flags, stream));
+}
+
+int inccl_reduce_f32_block(const float *const *srcs_dev, int R, float *dst_dev, size_t n, uint32_t *words_out_dev,
+                           int flags, void *stream)
+{
+    if (!srcs_dev) return inccl_set_error(INCCL_ERR_ARG, "srcs is NULL");
+    return kerr(inccl_k_block_fused((const void *const *)srcs_dev, R, dst_dev, n, words_out_dev, flags, R, 0, stream));
+}
+
+int inccl_stream_op_block(int in_kind, int out_kind, const void *const *srcs_dev, int R, void *dst_dev, size_t n,
+                          const uint32_t *words_dev, size_t elem_base, int scale_R, void *stream)
+{
+    if (!srcs_dev) return inccl_set_error(INCCL_ERR_ARG, "srcs is NULL");
+    if (scale_R < 0) return inccl_set_error(INCCL_ERR_ARG, "inccl_stream_op_block: scale_R %d is negative", scale_R);
+    return kerr(inccl_k_stream_block(in_kind, out_kind, srcs_dev, R, dst_dev, n, words_dev,
+                                     (elem_base + n + INCCL_BLOCK_ELEMS - 1) / INCCL_BLOCK_ELEMS, elem_base, scale_R, 0,
+                                     stream));
 }
 
 /* ---- ordering across caller streams ----
@@ -229,6 +260,10 @@ static int kind_pair_ok(int in_kind, int out_kind)
 struct inccl_op *inccl_op_create(int in_kind, int out_kind, const void *const *srcs_dev, int R, void *dst_dev,
                                  size_t n, int scale_exp, int scale_R, void *stream)
 {
+    if (scale_exp == INCCL_SCALE_BLOCK) {
+        block_refused("a prepared op");
+        return NULL;
+    }
     if (!kind_pair_ok(in_kind, out_kind) || !srcs_dev || R < 1 || R > INCCL_MAX_LOCAL_INPUTS ||
         (n > 0 && !dst_dev) || scale_exp < INCCL_SCALE_MIN || scale_exp > INCCL_SCALE_MAX || scale_R < 0) {
         inccl_set_error(INCCL_ERR_ARG, "inccl_op_create: invalid argument");
@@ -263,6 +298,10 @@ struct inccl_op *inccl_op_create_allreduce_f32(struct inccl_communicator *comm, 
         inccl_set_error(INCCL_ERR_ARG, "inccl_op_create_allreduce_f32: comm is NULL");
         return NULL;
     }
+    if (scale_exp == INCCL_SCALE_BLOCK) {
+        block_refused("a prepared op");
+        return NULL;
+    }
     if (scale_exp == INCCL_SCALE_AUTO) {   /* the auto scale is a per-call absmax: nothing to bind */
         inccl_set_error(INCCL_ERR_ARG, "inccl_op_create_allreduce_f32: a prepared op takes a fixed scale exponent");
         return NULL;
@@ -284,6 +323,10 @@ struct inccl_op *inccl_op_create_allreduce16(struct inccl_communicator *comm, in
 {
     if (!comm || (kind != INCCL_KIND_BF16 && kind != INCCL_KIND_F16)) {
         inccl_set_error(INCCL_ERR_ARG, "inccl_op_create_allreduce16: comm is NULL or kind is not BF16 / F16");
+        return NULL;
+    }
+    if (scale_exp == INCCL_SCALE_BLOCK) {
+        block_refused("a prepared op");
         return NULL;
     }
     if (scale_exp == INCCL_SCALE_AUTO) {
@@ -707,6 +750,7 @@ int inccl_communicator_destroy(struct inccl_communicator *comm)
     if (comm->d_f32) hipFree(comm->d_f32);
     if (comm->d_stage) hipFree(comm->d_stage);
     if (comm->d_words) hipFree(comm->d_words);
+    if (comm->d_bwords) hipFree(comm->d_bwords);
     inccl_copy_pool_destroy(comm->pool);
     inccl_d2h_worker_destroy(comm->d2h);
     if (comm->send_payload) hipHostFree(comm->send_payload);
@@ -879,6 +923,47 @@ int inccl_allreduce_q32(struct inccl_communicator *c, const int32_t *src_dev, in
     INCCL_ORDERED(c, stream, allreduce_q32_body(c, src_dev, dst_dev, n, stream));
 }
 
+/* INCCL_SCALE_BLOCK: one word per 256-element block of the fp32 bucket, its max
+ * over the ranks, in the communicator's d_bwords.  The max uses an exchange the
+ * engine already has: ncclAllReduce(max) of the nb words on the RCCL engines;
+ * on the in-process transport and the IPC engines each rank writes its words
+ * into row `me` of a zeroed W x nb int32 buffer, the engine's int32 allreduce
+ * gives every rank all W rows (adding zeros is exact) and k_words_max reduces
+ * them -- W / 256 of the bucket's bytes, no barrier or buffer of its own.
+ * Layout of d_bwords: the agreed words, zero (k = INCCL_SCALE_MAX, and the
+ * padding quantises zeros) up to the padded extent a sharded route may touch
+ * (n rounded up to W * 64, whole blocks), rounded to 64 words so that the rows
+ * behind them start 256-B aligned. */
+static int resolve_block_scale(struct inccl_communicator *c, const void *const *srcs, int R, size_t n, hipStream_t st,
+                               struct inccl_scale *sc)
+{
+    const int W = c->group->world_size, me = c->group->rank;
+    const size_t nb = (n + INCCL_BLOCK_ELEMS - 1) / INCCL_BLOCK_ELEMS;
+    const size_t agreed = ((n + (size_t)W * 64 + INCCL_BLOCK_ELEMS - 1) / INCCL_BLOCK_ELEMS + 1 + 63) / 64 * 64;
+    const int gather = W > 1 && (c->group->transport == INCCL_TRANSPORT_LOCAL || inccl_engine_is_ipc(c->engine));
+    const int flags = c->nonfinite == INCCL_NONFINITE_NAN ? INCCL_ABSMAX_FLAG_NONFINITE : 0;
+    int rc = inccl_ws_claim(c, st);
+    if (rc) return rc;
+    rc = inccl_ensure_dev(&c->d_bwords, &c->d_bwords_bytes, (agreed + (gather ? (size_t)W * nb : 0)) * sizeof(uint32_t));
+    if (rc) return rc;
+    uint32_t *words = (uint32_t *)c->d_bwords, *rows = words + agreed;
+    INCCL_HIP(hipMemsetAsync(words, 0, (agreed + (gather ? (size_t)W * nb : 0)) * sizeof(uint32_t), st));
+    rc = kerr(inccl_k_block_absmax(srcs, R, n, gather ? rows + (size_t)me * nb : words, flags, st));
+    if (rc) return rc;
+    if (gather) {
+        rc = inccl_tp_allreduce_q32(c, (const int32_t *)rows, (int32_t *)rows, (size_t)W * nb, st);
+        if (rc) return rc;
+        rc = kerr(inccl_k_words_max(rows, W, nb, words, st));
+    } else if (W > 1) {
+        rc = inccl_tp_allreduce_max_u32(c, words, nb, st);
+    }
+    if (rc) return rc;
+    sc->k = 0;
+    sc->blk = words;
+    sc->nb = agreed;
+    return 0;
+}
+
 /* The scale of one collective.  A fixed exponent passes through.  INCCL_SCALE_AUTO
  * takes the absmax of the local buckets (kind F32, BF16 or F16) and its max over
  * the group (with bit 31 set when a rank saw a NaN or +-Inf and the
@@ -894,6 +979,9 @@ static int resolve_scale(struct inccl_communicator *c, int kind, const void *con
     sc->k = scale_exp;
     sc->amax = NULL;
     sc->R = R * W;
+    sc->blk = NULL;
+    sc->nb = sc->blk_base = 0;
+    if (scale_exp == INCCL_SCALE_BLOCK) return resolve_block_scale(c, srcs, R, n, st, sc);
     if (scale_exp != INCCL_SCALE_AUTO) {
         if (scale_exp < INCCL_SCALE_MIN || scale_exp > INCCL_SCALE_MAX)
             return inccl_set_error(INCCL_ERR_ARG, "scale_exp %d out of range", scale_exp);
@@ -931,7 +1019,9 @@ static int resolve_scale(struct inccl_communicator *c, int kind, const void *con
 static int quant_sum(int kind, const void *const *srcs, int R, int32_t *q, size_t n, size_t total,
                      const struct inccl_scale *sc, hipStream_t st)
 {
-    const int rc = kerr(inccl_k_stream(kind, INCCL_KIND_Q32, srcs, R, q, n, sc->k, sc->amax, sc->R, st));
+    const int rc = sc->blk ? kerr(inccl_k_stream_block(kind, INCCL_KIND_Q32, srcs, R, q, n, sc->blk, sc->nb,
+                                                       sc->blk_base, sc->R, 0, st))
+                           : kerr(inccl_k_stream(kind, INCCL_KIND_Q32, srcs, R, q, n, sc->k, sc->amax, sc->R, st));
     if (rc) return rc;
     if (total > n) INCCL_HIP(hipMemsetAsync(q + n, 0, (total - n) * sizeof(int32_t), st));
     return 0;
@@ -947,13 +1037,17 @@ static int stage_quant(struct inccl_communicator *c, int kind, const void *const
     return 0;
 }
 
-/* dst[0, n) = the reduced int32 partials q dequantised to `kind` */
-static int stage_dequant(struct inccl_communicator *c, int kind, const int32_t *q, void *dst, size_t n,
+/* dst[0, n) = the reduced int32 partials q dequantised to `kind`; q[0] is
+ * element `lo` of the piece the scale belongs to (per-block exponents) */
+static int stage_dequant(struct inccl_communicator *c, int kind, const int32_t *q, void *dst, size_t n, size_t lo,
                          const struct inccl_scale *sc, hipStream_t st)
 {
     const void *s1[1] = {q};
     const int si = stage_open(c, st);
-    const int rc = kerr(inccl_k_stream_s(INCCL_KIND_Q32, kind, s1, 1, dst, n, sc->k, sc->amax, sc->R, c->out_shift, st));
+    const int rc = sc->blk ? kerr(inccl_k_stream_block(INCCL_KIND_Q32, kind, s1, 1, dst, n, sc->blk, sc->nb,
+                                                       sc->blk_base + lo, sc->R, c->out_shift, st))
+                           : kerr(inccl_k_stream_s(INCCL_KIND_Q32, kind, s1, 1, dst, n, sc->k, sc->amax, sc->R,
+                                                   c->out_shift, st));
     if (rc) return rc;
     stage_close(c, si, st, INCCL_STAGE_DEQUANT);
     return 0;
@@ -977,7 +1071,7 @@ static int allreduce_via_q32(struct inccl_communicator *c, int kind, const void 
     rc = inccl_tp_allreduce_q32(c, q, q, n, st);
     if (rc) return rc;
     stage_close(c, si, st, INCCL_STAGE_AR);
-    return stage_dequant(c, kind, q + lo, dst, cnt, sc, st);
+    return stage_dequant(c, kind, q + lo, dst, cnt, lo, sc, st);
 }
 
 /* Variant B, fp32 only: quant + local sum -> grouped
@@ -1045,7 +1139,7 @@ static int allreduce_piece(struct inccl_communicator *c, int kind, const void *c
     stage_close(c, si, st, INCCL_STAGE_RS);
     const int in_place = (total == n);
     char *gather = in_place ? (char *)dst : (char *)gws, *own = gather + (size_t)me * shard * es;
-    rc = stage_dequant(c, kind, qrecv, own, shard, sc, st);
+    rc = stage_dequant(c, kind, qrecv, own, shard, (size_t)me * shard, sc, st);
     if (rc) return rc;
     si = stage_open(c, st);
     rc = inccl_tp_all_gather(c, own, gather, shard, es, st);
@@ -1101,7 +1195,9 @@ static int allreduce_rsag(struct inccl_communicator *c, int kind, const void *co
     for (size_t off = 0; off < n; off += per) {
         const size_t cnt = (n - off) < per ? (n - off) : per;
         for (int r = 0; r < R; ++r) sub[r] = (const char *)srcs[r] + off * es;
-        rc = allreduce_piece(c, kind, sub, R, (char *)dst + off * es, cnt, sc, ws, c->d_f32, c->side_stream, st);
+        struct inccl_scale psc = *sc;   /* per-block exponents: the piece starts at element off */
+        psc.blk_base = off;
+        rc = allreduce_piece(c, kind, sub, R, (char *)dst + off * es, cnt, &psc, ws, c->d_f32, c->side_stream, st);
         if (rc) return rc;
         ws += inccl_shard_elems(cnt, W) * ((size_t)W + 1);
     }
@@ -1110,6 +1206,15 @@ static int allreduce_rsag(struct inccl_communicator *c, int kind, const void *co
 }
 
 static const char *const kind_names[] = {"f32", "", "", "bf16", "f16"};
+
+/* INCCL_SCALE_BLOCK on the FUSED route: one HBM pass, no words pass (the only
+ * rank's words are the agreed ones and stay in the kernel's registers) */
+static int block_fused(struct inccl_communicator *c, const void *const *srcs, int R, void *dst, size_t n,
+                       hipStream_t st)
+{
+    const int flags = c->nonfinite == INCCL_NONFINITE_NAN ? INCCL_ABSMAX_FLAG_NONFINITE : 0;
+    return kerr(inccl_k_block_fused(srcs, R, dst, n, NULL, flags, R * c->group->world_size, c->out_shift, st));
+}
 
 /* The allreduce of kind F32, BF16 or F16 buckets.  The int32 partial sums
  * travel alike for every kind (the switch's aggregate, nts.c:361-363); only the
@@ -1122,16 +1227,22 @@ static int allreduce_body(struct inccl_communicator *c, int kind, const void *co
 {
     if (!c || !srcs || R < 1 || R > INCCL_MAX_LOCAL_INPUTS || (!dst && n))
         return inccl_set_error(INCCL_ERR_ARG, "bad allreduce_%s args", kind_names[kind]);
+    if (scale_exp == INCCL_SCALE_BLOCK && kind != INCCL_KIND_F32) return block_refused("bf16 / fp16 buckets");
     for (int r = 0; r < R; ++r)
         if (!srcs[r] && n) return inccl_set_error(INCCL_ERR_ARG, "srcs[%d] is NULL", r);
     if (n == 0) return 0;
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    const int block = scale_exp == INCCL_SCALE_BLOCK;
+    enum inccl_route route =
+        inccl_route_of(INCCL_OP_ALLREDUCE, kind, c->group->transport, c->engine, c->group->world_size,
+                       c->force_sharded, c->mesh_rs, n, c->rccl_ar_bytes, c->ll_max_bytes);
+    if (block) {
+        route = inccl_route_block(route);
+        if (route == INCCL_ROUTE_FUSED) return block_fused(c, srcs, R, dst, n, st);
+    }
     struct inccl_scale sc;
     int rc = resolve_scale(c, kind, srcs, R, n, scale_exp, st, &sc);
     if (rc) return rc;
-    const enum inccl_route route =
-        inccl_route_of(INCCL_OP_ALLREDUCE, kind, c->group->transport, c->engine, c->group->world_size,
-                       c->force_sharded, c->mesh_rs, n, c->rccl_ar_bytes, c->ll_max_bytes);
     switch (route) {
         case INCCL_ROUTE_FUSED:   /* one HBM pass: quant + sum + dequant */
             return kerr(inccl_k_stream_s(kind, kind, srcs, R, dst, n, sc.k, sc.amax, sc.R, c->out_shift, st));
@@ -1204,6 +1315,7 @@ static int reduce_scatter_body(struct inccl_communicator *c, int kind, const voi
     const char *const name = kind_names[kind];
     if (!c || !srcs || R < 1 || R > INCCL_MAX_LOCAL_INPUTS || (!dst && n))
         return inccl_set_error(INCCL_ERR_ARG, "bad reduce_scatter_%s args", name);
+    if (scale_exp == INCCL_SCALE_BLOCK && kind != INCCL_KIND_F32) return block_refused("bf16 / fp16 buckets");
     for (int r = 0; r < R; ++r)
         if (!srcs[r] && n) return inccl_set_error(INCCL_ERR_ARG, "srcs[%d] is NULL", r);
     const int W = c->group->world_size, me = c->group->rank;
@@ -1217,14 +1329,18 @@ static int reduce_scatter_body(struct inccl_communicator *c, int kind, const voi
         if (d0 < s0 + n * es && s0 < d0 + shard * es)
             return inccl_set_error(INCCL_ERR_ARG, "reduce_scatter_%s: dst overlaps srcs[%d]", name, r);
     }
+    /* Every route is chosen from what all ranks share (engine, n, W and the
+     * knobs agreed in agree_knobs), never from this rank's dst alignment. */
+    enum inccl_route route =
+        inccl_route_of(INCCL_OP_REDUCE_SCATTER, kind, c->group->transport, c->engine, W, c->force_sharded, c->mesh_rs,
+                       n, c->rccl_ar_bytes, c->ll_max_bytes);
+    if (scale_exp == INCCL_SCALE_BLOCK) {
+        route = inccl_route_block(route);
+        if (route == INCCL_ROUTE_FUSED) return block_fused(c, srcs, R, dst, n, st);
+    }
     struct inccl_scale sc;
     int rc = resolve_scale(c, kind, srcs, R, n, scale_exp, st, &sc);
     if (rc) return rc;
-    /* Every route is chosen from what all ranks share (engine, n, W and the
-     * knobs agreed in agree_knobs), never from this rank's dst alignment. */
-    const enum inccl_route route =
-        inccl_route_of(INCCL_OP_REDUCE_SCATTER, kind, c->group->transport, c->engine, W, c->force_sharded, c->mesh_rs,
-                       n, c->rccl_ar_bytes, c->ll_max_bytes);
     switch (route) {
         case INCCL_ROUTE_FUSED:   /* one HBM pass */
             return kerr(inccl_k_stream_s(kind, kind, srcs, R, dst, n, sc.k, sc.amax, sc.R, c->out_shift, st));
@@ -1240,7 +1356,7 @@ static int reduce_scatter_body(struct inccl_communicator *c, int kind, const voi
             rc = inccl_tp_reduce_scatter_q32(c, qsend, qrecv, shard, st);
             if (rc) return rc;
             stage_close(c, si, st, INCCL_STAGE_RS);
-            return stage_dequant(c, kind, qrecv, dst, shard, &sc, st);
+            return stage_dequant(c, kind, qrecv, dst, shard, (size_t)me * shard, &sc, st);
         }
         case INCCL_ROUTE_AR_SHARD:   /* the engine's int32 allreduce, then the shard dequantised */
             return allreduce_via_q32(c, kind, srcs, R, dst, n, (size_t)me * shard, shard, &sc, st);
@@ -1577,6 +1693,7 @@ int inccl_allreduce_f32_host(struct inccl_communicator *c, const float *src_host
                              int scale_exp, size_t bucket_bytes)
 {
     if (!c || (!src_host && n) || (!dst_host && n)) return inccl_set_error(INCCL_ERR_ARG, "bad allreduce_f32_host args");
+    if (scale_exp == INCCL_SCALE_BLOCK) return block_refused("inccl_allreduce_f32_host");
     if (n == 0) return 0;
     INCCL_HIP(hipSetDevice(c->group->device));
     size_t B = bucket_bytes / sizeof(float);

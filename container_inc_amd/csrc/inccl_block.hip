@@ -1,0 +1,490 @@
+// inccl_block.hip -- per-block auto scaling (INCCL_SCALE_BLOCK) for fp32 buckets
+// on CDNA4 (gfx950).  One block is INCCL_BLOCK_ELEMS = 256 elements of the
+// bucket: lane t of a wave64 loads quad base + t, so one wave-wide dwordx4
+// access is one block when the base is a multiple of 64 quads.  Semantics
+// (tests/block_ref.py):
+//
+//   w_b   bits of max |x| over block b of every bucket of every rank (NaN
+//         ignored; with the non-finite flag a NaN or +-Inf sets bit 31)
+//   k_b   the auto scale rule on w_b (inccl_scale_rule.h: the integer form of
+//         choose_scale, a dozen integer ops, so that no kernel here runs a
+//         double-precision frexp)
+//   q = sat_i32(rne(x * 2^k_b)),  s = sum q mod 2^32,  y = (float)s * 2^-(k_b + out_shift)
+//
+// Kernels:
+//   k_stream_block_fused<R>      world 1, one HBM pass: the wave reduces its
+//                                block's absmax (six __shfl_xor steps), resolves
+//                                k_b and quantises + sums + dequantises the
+//                                quads it already holds; (R + 1) * 4 * n bytes
+//                                (+ n / 64 when the words are written out)
+//   k_block_fused_elem<R>        the same on buckets that are not 16-B aligned
+//   k_block_absmax<R, NF>        the words of R local buckets: one wave per block
+//                                and step, plain stores, overwrites
+//   k_stream_block<IN, OUT, R>   F32 -> Q32 (quantise + local sum) and Q32 -> F32
+//                                (sum + dequantise) at the agreed words; element i
+//                                of the call is element elem_base + i of the bucket
+//   k_stream_block_elem          the same per element (tails, elem_base % 4 != 0,
+//                                pointers not 16-B aligned)
+//   k_words_max                  element-wise unsigned max of W rows of words
+//
+// Only vector stores and plain C++.  Every lane of a wave reaches every
+// __shfl_xor: the loops and branches around them are wave-uniform.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "inccl_kernels.h"
+#include "inccl_scale_rule.h"
+#include "inccl_stream.h"
+
+namespace {
+
+using namespace inccl_dev;
+
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const uint32_t o = (uint32_t)__shfl_xor((int)v, off, 64);
+        v = v > o ? v : o;
+    }
+    return v;
+}
+
+// |x| bits; NaN -> 0 (ignored), or with NF a NaN / +-Inf -> bit 31 | its bits
+// (abs_bits of inccl_kernels.hip)
+template <bool NF>
+__device__ __forceinline__ uint32_t abs_bits(uint32_t b)
+{
+    const uint32_t a = b & 0x7fffffffu;
+    if constexpr (NF) return a >= 0x7f800000u ? 0x80000000u | a : a;
+    else return a > 0x7f800000u ? 0u : a;
+}
+
+template <bool NF>
+__device__ __forceinline__ uint32_t amax_quad(u32x4 x)
+{
+    return max(max(abs_bits<NF>(x.x), abs_bits<NF>(x.y)), max(abs_bits<NF>(x.z), abs_bits<NF>(x.w)));
+}
+
+// one block's multipliers from its word: 2^k_b to quantise, 2^-(k_b + out_shift)
+// to dequantise -- NaN when the word carries bit 31 (that block's results are NaN)
+struct BlockMul {
+    float scale, inv;
+};
+__device__ __forceinline__ BlockMul block_mul(uint32_t word, int scale_R, int out_shift)
+{
+    const int k = inccl_scale_of_word(word, scale_R);
+    BlockMul b;
+    b.scale = pow2f(k);
+    b.inv = (word >> 31) ? __builtin_nanf("") : pow2f(-k - out_shift);
+    return b;
+}
+
+__device__ __forceinline__ uint32_t fused1(uint32_t acc, float inv) { return store_xform<F32>(acc, inv); }
+
+template <int R, bool NF, int BLOCK, int U>
+__global__ __launch_bounds__(BLOCK) void k_stream_block_fused(SrcPtrs src, void* __restrict__ dst, int64_t n,
+                                                              uint32_t* __restrict__ words, int scale_R,
+                                                              int out_shift)
+{
+    const int64_t n4 = n >> 2;
+    const int tail = (int)(n & 3);                    // elements after the last quad: lane i == n4 takes them
+    const int64_t nq = ((n + 255) >> 8) << 6;         // quads of whole blocks: a wave for every block
+    const int64_t tile = (int64_t)BLOCK * U;
+    const int lane = threadIdx.x & 63;
+    u32x4* __restrict__ out = reinterpret_cast<u32x4*>(dst);
+    uint32_t* __restrict__ out1 = reinterpret_cast<uint32_t*>(dst);
+
+    for (int64_t base = (int64_t)blockIdx.x * tile; base < nq; base += (int64_t)gridDim.x * tile) {
+        const bool full = base + tile <= n4;
+        // every load of the tile in flight before the first compare
+        u32x4 v[R][U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int64_t i = base + threadIdx.x + (int64_t)u * BLOCK;
+#pragma unroll
+            for (int r = 0; r < R; ++r)
+                v[r][u] = (full || i < n4) ? __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(src.p[r]) + i)
+                                           : u32x4{0u, 0u, 0u, 0u};
+        }
+        __amdgpu_buffer_rsrc_t orsrc;
+        if (full) orsrc = __builtin_amdgcn_make_buffer_rsrc(out + base, 0, (int)(tile * 16), 0x00020000);
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int64_t i = base + threadIdx.x + (int64_t)u * BLOCK;
+            if (i - lane >= nq) continue;             // wave-uniform: this wave's block is past the bucket
+            uint32_t m = 0;
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const uint32_t a = amax_quad<NF>(v[r][u]);
+                m = m > a ? m : a;
+            }
+            const bool tl = tail != 0 && i == n4;
+            uint32_t t[R][3];
+            if (tl) {
+#pragma unroll
+                for (int r = 0; r < R; ++r)
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) {
+                        t[r][j] = j < tail ? reinterpret_cast<const uint32_t*>(src.p[r])[n4 * 4 + j] : 0u;
+                        const uint32_t a = abs_bits<NF>(t[r][j]);
+                        m = m > a ? m : a;
+                    }
+            }
+            // the block's word, wave-uniform: the exponent is resolved once per wave
+            const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max_u32(m));
+            const BlockMul bm = block_mul(w, scale_R, out_shift);
+            if (words != nullptr && lane == 0) words[i >> 6] = w;
+            u32x4 acc = {0u, 0u, 0u, 0u};
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                acc.x += quant1(__uint_as_float(v[r][u].x), bm.scale);
+                acc.y += quant1(__uint_as_float(v[r][u].y), bm.scale);
+                acc.z += quant1(__uint_as_float(v[r][u].z), bm.scale);
+                acc.w += quant1(__uint_as_float(v[r][u].w), bm.scale);
+            }
+            u32x4 o;
+            o.x = fused1(acc.x, bm.inv);
+            o.y = fused1(acc.y, bm.inv);
+            o.z = fused1(acc.z, bm.inv);
+            o.w = fused1(acc.w, bm.inv);
+            if (full)
+                __builtin_amdgcn_raw_buffer_store_b128(o, orsrc, (int)((threadIdx.x + u * BLOCK) * 16), 0, kAuxSc1);
+            else if (i < n4)
+                out[i] = o;
+            if (tl) {
+#pragma unroll
+                for (int j = 0; j < 3; ++j)
+                    if (j < tail) {
+                        uint32_t a = 0;
+#pragma unroll
+                        for (int r = 0; r < R; ++r) a += quant1(__uint_as_float(t[r][j]), bm.scale);
+                        out1[n4 * 4 + j] = fused1(a, bm.inv);
+                    }
+            }
+        }
+    }
+}
+
+constexpr int kBlkWaves = kBlock / 64;   // waves = blocks per workgroup and step of the per-block kernels
+
+// the fused kernel per element: lane t of the block's wave takes elements
+// 256 b + t + 64 j, j < 4 (coalesced dword accesses)
+template <int R, bool NF>
+__global__ __launch_bounds__(kBlock) void k_block_fused_elem(SrcPtrs src, void* __restrict__ dst, int64_t n,
+                                                             uint32_t* __restrict__ words, int scale_R, int out_shift)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t nb = (n + 255) >> 8;
+    uint32_t* __restrict__ out = reinterpret_cast<uint32_t*>(dst);
+    for (int64_t b = (int64_t)blockIdx.x * kBlkWaves + wave; b < nb; b += (int64_t)gridDim.x * kBlkWaves) {
+        uint32_t x[R][4];
+        uint32_t m = 0;
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int64_t e = (b << 8) + j * 64 + lane;
+                x[r][j] = e < n ? reinterpret_cast<const uint32_t*>(src.p[r])[e] : 0u;
+            }
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const uint32_t a = abs_bits<NF>(x[r][j]);
+                m = m > a ? m : a;
+            }
+        const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max_u32(m));
+        const BlockMul bm = block_mul(w, scale_R, out_shift);
+        if (words != nullptr && lane == 0) words[b] = w;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int64_t e = (b << 8) + j * 64 + lane;
+            if (e < n) {
+                uint32_t a = 0;
+#pragma unroll
+                for (int r = 0; r < R; ++r) a += quant1(__uint_as_float(x[r][j]), bm.scale);
+                out[e] = fused1(a, bm.inv);
+            }
+        }
+    }
+}
+
+// words[b] = max |x| bits over block b of the R buckets; vec: every bucket is 16-B aligned
+template <int R, bool NF>
+__global__ __launch_bounds__(kBlock) void k_block_absmax(SrcPtrs src, int64_t n, uint32_t* __restrict__ words,
+                                                         int vec)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t nb = (n + 255) >> 8, n4 = n >> 2;
+    const int tail = (int)(n & 3);
+    for (int64_t b = (int64_t)blockIdx.x * kBlkWaves + wave; b < nb; b += (int64_t)gridDim.x * kBlkWaves) {
+        uint32_t m = 0;
+        if (vec) {
+            const int64_t i = (b << 6) + lane;
+            if (i < n4) {
+                u32x4 v[R];
+#pragma unroll
+                for (int r = 0; r < R; ++r)
+                    v[r] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(src.p[r]) + i);
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    const uint32_t a = amax_quad<NF>(v[r]);
+                    m = m > a ? m : a;
+                }
+            } else if (i == n4) {
+#pragma unroll
+                for (int r = 0; r < R; ++r)
+                    for (int j = 0; j < tail; ++j) {
+                        const uint32_t a = abs_bits<NF>(reinterpret_cast<const uint32_t*>(src.p[r])[n4 * 4 + j]);
+                        m = m > a ? m : a;
+                    }
+            }
+        } else {
+#pragma unroll
+            for (int r = 0; r < R; ++r)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int64_t e = (b << 8) + j * 64 + lane;
+                    const uint32_t a = e < n ? abs_bits<NF>(reinterpret_cast<const uint32_t*>(src.p[r])[e]) : 0u;
+                    m = m > a ? m : a;
+                }
+        }
+        m = wave_max_u32(m);
+        if (lane == 0) words[b] = m;
+    }
+}
+
+// the word of the bucket's block `blk`, clamped to the words the caller holds
+__device__ __forceinline__ uint32_t word_at(const uint32_t* __restrict__ words, int64_t blk, int64_t nb)
+{
+    return words[blk < nb ? blk : nb - 1];
+}
+
+// out = OUT(sum_r IN(src_r)) over quads, <F32, Q32> or <Q32, F32>; quad i holds
+// the bucket's elements elem_base + 4 i .. + 3, inside one block since
+// elem_base % 4 == 0
+template <int IN, int OUT, int R, int BLOCK>
+__global__ __launch_bounds__(BLOCK) void k_stream_block(SrcPtrs src, void* __restrict__ dst, int64_t n4,
+                                                        const uint32_t* __restrict__ words, int64_t nb,
+                                                        int64_t elem_base, int scale_R, int out_shift)
+{
+    u32x4* __restrict__ out = reinterpret_cast<u32x4*>(dst);
+    for (int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x; i < n4; i += (int64_t)gridDim.x * BLOCK) {
+        u32x4 v[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) v[r] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(src.p[r]) + i);
+        const BlockMul bm = block_mul(word_at(words, (elem_base + (i << 2)) >> 8, nb), scale_R, out_shift);
+        u32x4 acc = {0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            acc.x += load_xform<IN>(v[r].x, bm.scale);
+            acc.y += load_xform<IN>(v[r].y, bm.scale);
+            acc.z += load_xform<IN>(v[r].z, bm.scale);
+            acc.w += load_xform<IN>(v[r].w, bm.scale);
+        }
+        u32x4 o;
+        o.x = store_xform<OUT>(acc.x, bm.inv);
+        o.y = store_xform<OUT>(acc.y, bm.inv);
+        o.z = store_xform<OUT>(acc.z, bm.inv);
+        o.w = store_xform<OUT>(acc.w, bm.inv);
+        out[i] = o;
+    }
+}
+
+template <int IN, int OUT, int R>
+__global__ __launch_bounds__(kBlock) void k_stream_block_elem(SrcPtrs src, void* __restrict__ dst, int64_t begin,
+                                                              int64_t n, const uint32_t* __restrict__ words,
+                                                              int64_t nb, int64_t elem_base, int scale_R,
+                                                              int out_shift)
+{
+    uint32_t* __restrict__ out = reinterpret_cast<uint32_t*>(dst);
+    for (int64_t i = begin + (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
+        const BlockMul bm = block_mul(word_at(words, (elem_base + i) >> 8, nb), scale_R, out_shift);
+        uint32_t acc = 0;
+#pragma unroll
+        for (int r = 0; r < R; ++r) acc += load_xform<IN>(reinterpret_cast<const uint32_t*>(src.p[r])[i], bm.scale);
+        out[i] = store_xform<OUT>(acc, bm.inv);
+    }
+}
+
+// out[b] = max_j rows[j * nb + b]
+__global__ __launch_bounds__(kBlock) void k_words_max(const uint32_t* __restrict__ rows, int W, int64_t nb,
+                                                      uint32_t* __restrict__ out)
+{
+    for (int64_t b = (int64_t)blockIdx.x * kBlock + threadIdx.x; b < nb; b += (int64_t)gridDim.x * kBlock) {
+        uint32_t m = 0;
+        for (int j = 0; j < W; ++j) {
+            const uint32_t w = rows[(int64_t)j * nb + b];
+            m = m > w ? m : w;
+        }
+        out[b] = m;
+    }
+}
+
+// ---------------------------------------------------------------------------
+// host-side dispatch
+// ---------------------------------------------------------------------------
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+int grid_cap()
+{
+    static int cus = 0;
+    if (cus == 0) {
+        int dev = 0, v = 0;
+        if (hipGetDevice(&dev) == hipSuccess &&
+            hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
+            cus = v;
+        else
+            cus = 256;
+    }
+    return cus * 8;
+}
+
+int grid_of(int64_t items, int per_group)
+{
+    const int64_t g = (items + per_group - 1) / per_group, cap = grid_cap();
+    return (int)(g < 1 ? 1 : (g < cap ? g : cap));
+}
+
+int fill_srcs(const void* const* srcs, int R, SrcPtrs* s, bool* vec)
+{
+    if (srcs == nullptr || R < 1 || R > kMaxR) return INCCL_ERR_ARG;
+    *s = SrcPtrs{};
+    for (int r = 0; r < R; ++r) {
+        if (srcs[r] == nullptr) return INCCL_ERR_ARG;
+        s->p[r] = srcs[r];
+        *vec = *vec && aligned16(srcs[r]);
+    }
+    return 0;
+}
+
+template <int R, bool NF>
+void launch_fused(const SrcPtrs& s, void* dst, int64_t n, uint32_t* words, int scale_R, int out_shift, bool vec,
+                  hipStream_t st)
+{
+    const int64_t nb = (n + 255) >> 8;
+    if (vec) {
+        constexpr int B = Geometry<R>::BLOCK, U = Geometry<R>::U;
+        // one workgroup per tile, as the single-scale fused kernel
+        const int64_t tiles = (nb * 64 + (int64_t)B * U - 1) / ((int64_t)B * U);
+        const int grid = (int)(tiles < 0x7fffffff ? tiles : 0x7fffffff);
+        hipLaunchKernelGGL((k_stream_block_fused<R, NF, B, U>), dim3(grid), dim3(B), 0, st, s, dst, n, words, scale_R,
+                           out_shift);
+    } else {
+        hipLaunchKernelGGL((k_block_fused_elem<R, NF>), dim3(grid_of(nb, kBlkWaves)), dim3(kBlock), 0, st, s, dst, n,
+                           words, scale_R, out_shift);
+    }
+}
+
+template <int R, bool NF>
+void launch_absmax(const SrcPtrs& s, int64_t n, uint32_t* words, bool vec, hipStream_t st)
+{
+    hipLaunchKernelGGL((k_block_absmax<R, NF>), dim3(grid_of((n + 255) >> 8, kBlkWaves)), dim3(kBlock), 0, st, s, n,
+                       words, vec ? 1 : 0);
+}
+
+template <int IN, int OUT, int R>
+void launch_stream(const SrcPtrs& s, void* dst, int64_t n, const uint32_t* words, int64_t nb, int64_t elem_base,
+                   int scale_R, int out_shift, bool vec, hipStream_t st)
+{
+    constexpr int B = 512;
+    int64_t done = 0;
+    if (vec && (elem_base & 3) == 0) {
+        const int64_t n4 = n >> 2;
+        if (n4 > 0)
+            hipLaunchKernelGGL((k_stream_block<IN, OUT, R, B>), dim3(grid_of(n4, B)), dim3(B), 0, st, s, dst, n4, words,
+                               nb, elem_base, scale_R, out_shift);
+        done = n4 << 2;
+    }
+    if (done < n)
+        hipLaunchKernelGGL((k_stream_block_elem<IN, OUT, R>), dim3(grid_of(n - done, kBlock)), dim3(kBlock), 0, st, s,
+                           dst, done, n, words, nb, elem_base, scale_R, out_shift);
+}
+
+#define INCCL_R_SWITCH(R, CALL) \
+    switch (R) {                \
+        case 1: CALL(1); break; \
+        case 2: CALL(2); break; \
+        case 3: CALL(3); break; \
+        case 4: CALL(4); break; \
+        case 5: CALL(5); break; \
+        case 6: CALL(6); break; \
+        case 7: CALL(7); break; \
+        default: CALL(8); break; \
+    }
+
+}  // namespace
+
+extern "C" {
+
+int inccl_k_block_absmax(const void* const* srcs, int R, size_t n, uint32_t* words_dev, int flags, void* stream)
+{
+    SrcPtrs s;
+    bool vec = true;
+    if (fill_srcs(srcs, R, &s, &vec) || (flags & ~INCCL_ABSMAX_FLAG_NONFINITE) || (words_dev == nullptr && n > 0))
+        return INCCL_ERR_ARG;
+    if (n == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+#define INCCL_CALL(RR)                                                       \
+    if (flags) launch_absmax<RR, true>(s, (int64_t)n, words_dev, vec, st);  \
+    else launch_absmax<RR, false>(s, (int64_t)n, words_dev, vec, st)
+    INCCL_R_SWITCH(R, INCCL_CALL)
+#undef INCCL_CALL
+    return (int)hipGetLastError();
+}
+
+int inccl_k_block_fused(const void* const* srcs, int R, void* dst, size_t n, uint32_t* words_out_dev, int flags,
+                        int scale_R, int out_shift, void* stream)
+{
+    SrcPtrs s;
+    bool vec = aligned16(dst);
+    if (fill_srcs(srcs, R, &s, &vec) || (flags & ~INCCL_ABSMAX_FLAG_NONFINITE) || (dst == nullptr && n > 0) ||
+        out_shift < 0 || out_shift > 8)
+        return INCCL_ERR_ARG;
+    if (n == 0) return 0;
+    if (scale_R <= 0) scale_R = R;
+    hipStream_t st = (hipStream_t)stream;
+#define INCCL_CALL(RR)                                                                                    \
+    if (flags) launch_fused<RR, true>(s, dst, (int64_t)n, words_out_dev, scale_R, out_shift, vec, st);   \
+    else launch_fused<RR, false>(s, dst, (int64_t)n, words_out_dev, scale_R, out_shift, vec, st)
+    INCCL_R_SWITCH(R, INCCL_CALL)
+#undef INCCL_CALL
+    return (int)hipGetLastError();
+}
+
+int inccl_k_stream_block(int in_kind, int out_kind, const void* const* srcs, int R, void* dst, size_t n,
+                         const uint32_t* words_dev, size_t nb, size_t elem_base, int scale_R, int out_shift,
+                         void* stream)
+{
+    SrcPtrs s;
+    bool vec = aligned16(dst);
+    const bool quant = in_kind == F32 && out_kind == Q32, deq = in_kind == Q32 && out_kind == F32;
+    if (fill_srcs(srcs, R, &s, &vec) || (!quant && !deq) || (dst == nullptr && n > 0) || out_shift < 0 ||
+        out_shift > 8 || ((words_dev == nullptr || nb == 0) && n > 0))
+        return INCCL_ERR_ARG;
+    if (n == 0) return 0;
+    if (scale_R <= 0) scale_R = R;
+    hipStream_t st = (hipStream_t)stream;
+#define INCCL_CALL(RR)                                                                                        \
+    if (quant)                                                                                                \
+        launch_stream<F32, Q32, RR>(s, dst, (int64_t)n, words_dev, (int64_t)nb, (int64_t)elem_base, scale_R,   \
+                                    out_shift, vec, st);                                                      \
+    else                                                                                                      \
+        launch_stream<Q32, F32, RR>(s, dst, (int64_t)n, words_dev, (int64_t)nb, (int64_t)elem_base, scale_R,   \
+                                    out_shift, vec, st)
+    INCCL_R_SWITCH(R, INCCL_CALL)
+#undef INCCL_CALL
+    return (int)hipGetLastError();
+}
+
+int inccl_k_words_max(const uint32_t* rows_dev, int W, size_t nb, uint32_t* out_dev, void* stream)
+{
+    if (W < 1 || ((rows_dev == nullptr || out_dev == nullptr) && nb > 0)) return INCCL_ERR_ARG;
+    if (nb == 0) return 0;
+    hipLaunchKernelGGL(k_words_max, dim3(grid_of((int64_t)nb, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, rows_dev,
+                       W, (int64_t)nb, out_dev);
+    return (int)hipGetLastError();
+}
+
+}  // extern "C"

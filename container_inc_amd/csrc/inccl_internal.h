@@ -72,6 +72,9 @@ struct inccl_communicator {
     void *d_stage;               /* host-path device staging (2 x in + 2 x out buckets) */
     size_t d_stage_bytes;
     uint32_t *d_words;           /* small scratch words: [0] absmax, [1] checksum */
+    void *d_bwords;              /* INCCL_SCALE_BLOCK: the agreed block words, then the W rows they are
+                                  * gathered in (api.c resolve_block_scale); freed beside d_words */
+    size_t d_bwords_bytes;
     /* p2p engine: library-owned buffers shared with every peer through HIP IPC
      * handles; each GPU pulls its shard from all peers over xGMI */
     int engine;                  /* INCCL_ENGINE_* */
@@ -160,11 +163,16 @@ int inccl_rccl_alltoall_q32(struct inccl_communicator *c, const int32_t *send, i
 /* The scale of one collective call (api.c resolve_scale), as the engines and
  * the kernels take it: a fixed exponent k, or the device absmax word the
  * kernels resolve the exponent from (k unused then), and the number of buckets
- * summed over the whole group. */
+ * summed over the whole group.  INCCL_SCALE_BLOCK: blk points at the agreed word
+ * of the bucket's block 0 (nb of them; k and amax unused) and blk_base is where
+ * the piece this scale is handed to starts in the bucket, in elements.  Only
+ * the stage helpers of api.c take such a scale (inccl_route_block). */
 struct inccl_scale {
     int k;
     const uint32_t *amax;
     int R;
+    const uint32_t *blk;
+    size_t nb, blk_base;
 };
 
 /* p2p engine (p2p.c): allreduce and reduce-scatter of kind F32 / BF16 / F16

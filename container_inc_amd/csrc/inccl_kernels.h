@@ -23,6 +23,21 @@ int inccl_k_absmax(int kind, const void *const *srcs, int R, size_t n, uint32_t 
                    void *stream);
 int inccl_k_checksum(const int32_t *q, size_t n, uint64_t index_base, uint32_t *out_dev, int zero_first,
                      void *stream);
+/* per-block auto scaling of fp32 buckets (inccl_block.hip; include/inccl_amd.h INCCL_SCALE_BLOCK).
+ * flags: 0 or INCCL_ABSMAX_FLAG_NONFINITE.
+ *   block_absmax  words[b] = the absmax word of block b of the R buckets, ceil(n / 256) words, overwritten
+ *   block_fused   dst = dequant(sum_r quant(srcs[r])) at each block's own exponent, resolved in the
+ *                 kernel for scale_R contributors; words_out (NULL ok) receives the words
+ *   stream_block  F32 -> Q32 or Q32 -> F32 at the agreed words: element i is element elem_base + i of
+ *                 the bucket whose block 0 words_dev points at; a block index past nb - 1 reads word nb - 1
+ *   words_max     out[b] = max_j rows[j * nb + b] (unsigned) */
+int inccl_k_block_absmax(const void *const *srcs, int R, size_t n, uint32_t *words_dev, int flags, void *stream);
+int inccl_k_block_fused(const void *const *srcs, int R, void *dst, size_t n, uint32_t *words_out_dev, int flags,
+                        int scale_R, int out_shift, void *stream);
+int inccl_k_stream_block(int in_kind, int out_kind, const void *const *srcs, int R, void *dst, size_t n,
+                         const uint32_t *words_dev, size_t nb, size_t elem_base, int scale_R, int out_shift,
+                         void *stream);
+int inccl_k_words_max(const uint32_t *rows_dev, int W, size_t nb, uint32_t *out_dev, void *stream);
 void inccl_k_set_tuning(int grid_cap, int nt_loads);
 /* p2p engine kernels reading peer memory with system-coherent loads (inccl_peer.hip).
  * The pull-reduce, n % 4 == 0, by out_kind:

@@ -83,4 +83,24 @@ static inline enum inccl_route inccl_route_of(int op, int kind, int transport, i
     return INCCL_ROUTE_AR;
 }
 
+/* The route a call with INCCL_SCALE_BLOCK takes instead of `route`: per-block
+ * exponents travel through the stage helpers only (quantise at the agreed words
+ * -> an int32 exchange -> dequantise), so the routes built from those stay, and
+ * the engines' own exchanges, which carry one scale per call (a2a's fused sum +
+ * dequantise, the p2p / ll / mesh kernels), give way to the same engine's int32
+ * allreduce.  FUSED stays: it becomes the one-pass per-block kernel. */
+static inline enum inccl_route inccl_route_block(enum inccl_route route)
+{
+    switch (route) {
+        case INCCL_ROUTE_A2A:
+        case INCCL_ROUTE_IPC_P2P:
+        case INCCL_ROUTE_IPC_LL:
+        case INCCL_ROUTE_IPC_MESH: return INCCL_ROUTE_AR;
+        case INCCL_ROUTE_IPC_MESH_RS:
+        case INCCL_ROUTE_IPC_LL_RS:
+        case INCCL_ROUTE_IPC_P2P_RS: return INCCL_ROUTE_AR_SHARD;
+        default: return route;
+    }
+}
+
 #endif

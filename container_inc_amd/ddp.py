@@ -21,12 +21,28 @@ it would after a float allreduce.  (The quantiser alone would map NaN to 0 and
 saturate +-Inf: a finite, wrong gradient.)  The averaged result is bit-identical to the oracle's
 ``reduce_f32`` of the same buckets divided by the world size.
 
+``scale_exp=inccl.SCALE_BLOCK`` (fp32 buckets only) gives every 256-element
+block of the bucket its own auto exponent instead: a flat bucket concatenates
+parameters whose gradients differ by orders of magnitude, and under
+``SCALE_AUTO`` the largest one sets the exponent for all of them (a LayerNorm
+gain next to an embedding row keeps few or no significant bits).  The mean and
+the non-finite mode apply alike, the latter per block: only the blocks that
+held a NaN or +-Inf come out NaN.  A bf16 / fp16 bucket in this mode raises.
+
 fp32, bf16 and fp16 CUDA buckets are accepted (bf16 / fp16 through
 ``inccl_allreduce_bf16`` / ``_f16``: the same int32 sums, the result rounded to
 the bucket's format).  For a power-of-two world the mean comes out of the
 dequantise stage itself (``inccl_comm_set_average``: scale 2^-(k + log2 W)),
 for every format alike; otherwise the hook divides by W in torch.  Anything
 else raises (no silent fallback to another collective).
+
+Teardown: the hook runs every bucket on the communicator's own stream and marks
+it as used there (``record_stream``), and torch's caching allocator records an
+event on that stream when such a bucket is freed.  So drop the DDP model (and
+anything else that holds its buckets), ``torch.cuda.synchronize()`` and
+``torch.cuda.empty_cache()`` before ``comm.destroy()``: a rank that destroyed
+its communicator first, with the model still alive, crashed at exit
+(tests/_block_ddp_rank.py keeps this order).
 """
 from __future__ import annotations
 
@@ -67,11 +83,18 @@ class HookState:
         return self.folded
 
     def apply_nonfinite(self) -> None:
-        """Once: the communicator's non-finite mode (auto scale only)."""
+        """Once: the communicator's non-finite mode (auto scale and per-block scale only)."""
         if not self._nonfinite_set:
             self._nonfinite_set = True
             if hasattr(self.comm, "set_nonfinite"):
                 self.comm.set_nonfinite(self.propagate_nonfinite)
+
+    def check_format(self, dtype) -> None:
+        """Per-block scaling serves fp32 buckets only: say so here, by name."""
+        import torch
+        if self.scale_exp == inccl.SCALE_BLOCK and dtype != torch.float32:
+            raise IncclError(f"inccl hook: scale_exp=SCALE_BLOCK (per-block auto scaling) takes fp32 gradients only, "
+                             f"got {dtype}; use SCALE_AUTO for bf16 / fp16 buckets")
 
     @property
     def world_size(self) -> int:
@@ -93,6 +116,7 @@ def allreduce_hook(state: HookState, bucket):
     name = {torch.float32: "allreduce_f32", torch.bfloat16: "allreduce_bf16", torch.float16: "allreduce_f16"}.get(buf.dtype)
     if name is None:
         raise IncclError(f"inccl DDP hook: fp32, bf16 or fp16 gradient buckets only, got {buf.dtype}")
+    state.check_format(buf.dtype)
     reduce = getattr(state.comm, name)
     state.apply_nonfinite()
     w = state.world_size
@@ -147,7 +171,9 @@ def communicator_from_env(port_offset: int = 17, device: int | None = None, engi
 
 
 def register(ddp_model, comm, scale_exp: int = inccl.SCALE_AUTO, average: bool = True) -> HookState:
-    """Route every gradient bucket of ``ddp_model`` through ``comm``; returns the hook state."""
+    """Route every gradient bucket of ``ddp_model`` through ``comm``; returns the hook
+    state.  ``scale_exp``: a fixed exponent, ``SCALE_AUTO`` (one per bucket) or
+    ``SCALE_BLOCK`` (one per 256-element block, fp32 buckets)."""
     state = HookState(comm=comm, scale_exp=scale_exp, average=average)
     ddp_model.register_comm_hook(state, allreduce_hook)
     return state

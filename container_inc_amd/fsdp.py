@@ -20,6 +20,11 @@ skips the step on every rank.  Both change the communicator: give the hook one
 of its own.  The collective runs on the current stream -- FSDP calls its hook
 on its own post-backward stream already -- so the shard is ready for FSDP's next
 use without further synchronisation.  fp32, bf16 and fp16 gradients.
+
+``register(..., scale_exp=inccl.SCALE_BLOCK)`` (fp32 gradients only) scales
+every 256-element block of the unsharded gradient on its own, shards included:
+a shard is dequantised at the exponents of the blocks it lies in, wherever it
+starts.  A bf16 / fp16 gradient in this mode raises.
 """
 from __future__ import annotations
 
@@ -31,6 +36,7 @@ def _check(state: HookState, grad):
     import torch
     if grad.dtype not in (torch.float32, torch.bfloat16, torch.float16):
         raise IncclError(f"inccl FSDP hook: fp32, bf16 or fp16 gradients only, got {grad.dtype}")
+    state.check_format(grad.dtype)
     state.apply_nonfinite()
     w = state.world_size
     return w, state.average and w > 1 and not state.fold_average()

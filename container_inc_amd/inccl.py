@@ -22,6 +22,8 @@ from ._lib import IncclError, check, load
 
 KIND_F32, KIND_Q32, KIND_Q32BE, KIND_BF16, KIND_F16 = 0, 1, 2, 3, 4
 SCALE_MIN, SCALE_MAX, SCALE_AUTO = -64, 64, 0x7FFFFFFF
+SCALE_BLOCK = 0x7FFFFFFE         # inccl_amd.h INCCL_SCALE_BLOCK: one auto exponent per BLOCK_ELEMS elements (fp32)
+BLOCK_ELEMS = 256
 MAX_LOCAL_INPUTS = 8
 ABSMAX_FLAG_NONFINITE = 2        # inccl_amd.h INCCL_ABSMAX_FLAG_NONFINITE
 NONFINITE_SATURATE, NONFINITE_NAN = 0, 1
@@ -67,7 +69,7 @@ def _ptr_array(ptrs: Sequence[int]):
 
 def _check_scale(k: int) -> int:
     k = int(k)
-    if k != SCALE_AUTO and not (SCALE_MIN <= k <= SCALE_MAX):
+    if k not in (SCALE_AUTO, SCALE_BLOCK) and not (SCALE_MIN <= k <= SCALE_MAX):
         raise ValueError(f"scale exponent {k} outside [{SCALE_MIN}, {SCALE_MAX}]")
     return k
 
@@ -261,6 +263,66 @@ def reduce_f32_auto(srcs, out=None, word=None, stream=None):
     rc = load().inccl_reduce_f32_auto(_ptr_array(ptrs), len(ptrs), _dev_ptr(out, torch.float32, "out", n), n,
                                       _dev_ptr(word, torch.int32, "word", 1), _stream_handle(stream))
     check(rc, "inccl_reduce_f32_auto")
+    return out
+
+
+def _nblocks(n: int) -> int:
+    return (n + BLOCK_ELEMS - 1) // BLOCK_ELEMS
+
+
+def block_absmax(srcs, words=None, nonfinite_flag: bool = False, stream=None):
+    """The absmax words of R fp32 buckets, one per 256-element block
+    (inccl_block_absmax_f32), as an int32 tensor of ceil(n / 256) float-bit words."""
+    torch = _torch()
+    srcs = list(srcs)
+    n = srcs[0].numel()
+    ptrs = [_dev_ptr(s, torch.float32, f"srcs[{i}]", n) for i, s in enumerate(srcs)]
+    if words is None:
+        words = torch.empty(_nblocks(n), dtype=torch.int32, device=srcs[0].device)
+    rc = load().inccl_block_absmax_f32(_ptr_array(ptrs), len(ptrs), n, _dev_ptr(words, torch.int32, "words", _nblocks(n)),
+                                       ABSMAX_FLAG_NONFINITE if nonfinite_flag else 0, _stream_handle(stream))
+    check(rc, "inccl_block_absmax_f32")
+    return words
+
+
+def reduce_f32_block(srcs, out=None, words=None, nonfinite_flag: bool = False, stream=None):
+    """Fused single-GPU bucket reduce with one auto exponent per 256-element
+    block, in one HBM pass (inccl_reduce_f32_block); `words` (optional int32
+    tensor of ceil(n / 256)) receives the blocks' absmax words."""
+    torch = _torch()
+    srcs = list(srcs)
+    n = srcs[0].numel()
+    ptrs = [_dev_ptr(s, torch.float32, f"srcs[{i}]", n) for i, s in enumerate(srcs)]
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device=srcs[0].device)
+    wptr = None if words is None else _dev_ptr(words, torch.int32, "words", _nblocks(n))
+    rc = load().inccl_reduce_f32_block(_ptr_array(ptrs), len(ptrs), _dev_ptr(out, torch.float32, "out", n), n, wptr,
+                                       ABSMAX_FLAG_NONFINITE if nonfinite_flag else 0, _stream_handle(stream))
+    check(rc, "inccl_reduce_f32_block")
+    return out
+
+
+def stream_op_block(in_kind: int, out_kind: int, srcs, words, out=None, elem_base: int = 0, scale_R: int = 0,
+                    n: int | None = None, stream=None):
+    """``stream_op`` F32 -> Q32 or Q32 -> F32 at agreed per-block words
+    (inccl_stream_op_block): ``words[0]`` is the word of the bucket's block 0 and
+    element i of the call is element ``elem_base + i`` of that bucket."""
+    torch = _torch()
+    srcs = list(srcs)
+    if len(srcs) < 1 or len(srcs) > MAX_LOCAL_INPUTS:
+        raise ValueError(f"1..{MAX_LOCAL_INPUTS} inputs per launch, got {len(srcs)}")
+    if elem_base < 0:
+        raise ValueError(f"elem_base {elem_base} is negative")
+    in_dt, out_dt = getattr(torch, _TORCH_KIND[in_kind]), getattr(torch, _TORCH_KIND[out_kind])
+    if n is None:
+        n = srcs[0].numel()
+    ptrs = [_dev_ptr(s, in_dt, f"srcs[{i}]", n) for i, s in enumerate(srcs)]
+    if out is None:
+        out = torch.empty(n, dtype=out_dt, device=srcs[0].device)
+    wptr = _dev_ptr(words, torch.int32, "words", _nblocks(int(elem_base) + n))
+    rc = load().inccl_stream_op_block(in_kind, out_kind, _ptr_array(ptrs), len(ptrs), _dev_ptr(out, out_dt, "out", n), n,
+                                      wptr, int(elem_base), int(scale_R), _stream_handle(stream))
+    check(rc, "inccl_stream_op_block")
     return out
 
 

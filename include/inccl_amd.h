@@ -19,6 +19,9 @@
  *   dequantise  y = (float)s * 2^-k                       ((float) rounds to nearest even)
  *   k in [INCCL_SCALE_MIN, INCCL_SCALE_MAX]; INCCL_SCALE_AUTO picks the largest k
  *   with R_total * max|x| * 2^k <= 2^30 from a device-side absmax reduction.
+ *   INCCL_SCALE_BLOCK (fp32 buckets) applies that rule to every block of
+ *   INCCL_BLOCK_ELEMS elements on its own: one exponent per block instead of
+ *   one per bucket, so an outlier costs only its own block its precision.
  */
 #ifndef INCCL_AMD_H
 #define INCCL_AMD_H
@@ -36,6 +39,8 @@ extern "C" {
 #define INCCL_SCALE_MIN (-64)
 #define INCCL_SCALE_MAX 64
 #define INCCL_SCALE_AUTO 0x7fffffff
+#define INCCL_SCALE_BLOCK 0x7ffffffe    /* one auto exponent per INCCL_BLOCK_ELEMS elements (fp32 buckets) */
+#define INCCL_BLOCK_ELEMS 256           /* one wave64 dwordx4 access, one reference packet payload */
 
 #define INCCL_OK 0
 #define INCCL_ERR_ARG (-1)
@@ -110,6 +115,35 @@ int inccl_op_destroy(struct inccl_op *op);
 #define INCCL_ABSMAX_FLAG_NONFINITE 2
 int inccl_absmax_f32(const float *const *srcs_dev, int R, size_t n, uint32_t *amax_bits_dev, int zero_first,
                      void *stream);
+/* ---- per-block auto scaling (INCCL_SCALE_BLOCK), fp32 buckets ----
+ * Block b is elements [256 b, min(n, 256 (b + 1))) of the bucket; the partial
+ * last block is an ordinary block.  Its word w_b is the absmax word of block b
+ * of every bucket (of every rank: an unsigned max over words), its exponent
+ * k_b = inccl_choose_scale_word(w_b, R_total); every element of the block is
+ * quantised, summed and dequantised at k_b.  A block holding +-Inf gets
+ * INCCL_SCALE_MIN and saturates; a word with bit 31
+ * (INCCL_ABSMAX_FLAG_NONFINITE) makes that block's results NaN and leaves every
+ * other block as it would be without it.  `flags`: 0 or
+ * INCCL_ABSMAX_FLAG_NONFINITE.  A fixed-exponent function handed
+ * INCCL_SCALE_BLOCK as its scale_exp fails with INCCL_ERR_ARG.
+ *
+ * The words of R local buckets: words_dev[0 .. ceil(n / 256)), overwritten. */
+int inccl_block_absmax_f32(const float *const *srcs_dev, int R, size_t n, uint32_t *words_dev, int flags,
+                           void *stream);
+/* Fused single-GPU bucket reduce at per-block exponents, R_total = R, in ONE
+ * HBM pass -- (R + 1) * 4 * n bytes (+ n / 64 for the words), against the
+ * (2 R + 1) * 4 * n of inccl_reduce_f32_auto, which reads the buckets twice:
+ * each wave reduces the absmax of the block it already holds in registers.
+ * words_out_dev (NULL ok) receives the ceil(n / 256) words.  dst may alias srcs[0]. */
+int inccl_reduce_f32_block(const float *const *srcs_dev, int R, float *dst_dev, size_t n, uint32_t *words_out_dev,
+                           int flags, void *stream);
+/* inccl_stream_op at agreed words, kinds F32 -> Q32 (quantise + local sum) and
+ * Q32 -> F32 (sum + dequantise).  words_dev points at the word of the bucket's
+ * block 0 and element i of the call is element elem_base + i of that bucket (a
+ * shard or a pipelined piece of it), so it must hold ceil((elem_base + n) / 256)
+ * words.  scale_R: the contributors the exponents are chosen for (0: R). */
+int inccl_stream_op_block(int in_kind, int out_kind, const void *const *srcs_dev, int R, void *dst_dev, size_t n,
+                          const uint32_t *words_dev, size_t elem_base, int scale_R, void *stream);
 /* Position-weighted linear checksum sum_i (2(base+i)+1)*q[i] mod 2^32 into *out_dev. */
 int inccl_checksum_q32(const int32_t *q_dev, size_t n, uint64_t index_base, uint32_t *out_dev, int zero_first,
                        void *stream);
@@ -257,7 +291,16 @@ int inccl_comm_stage_times(struct inccl_communicator *comm, double *us, int kind
  *   dst = dequant( sum over ranks, sum over r<R  quant(srcs[r]) )
  * world == 1: one fused kernel.  world > 1: quant+local sum -> reduce-scatter
  * (int32, sum) -> dequantise own shard -> all-gather (fp32).  `scale_exp` may be
- * INCCL_SCALE_AUTO (adds an absmax pass and a 4-byte max-allreduce).
+ * INCCL_SCALE_AUTO (adds an absmax pass and a 4-byte max-allreduce) or
+ * INCCL_SCALE_BLOCK (fp32 only; also inccl_allreduce_f32_pipelined and
+ * inccl_reduce_scatter_f32): world 1 is the one-pass inccl_reduce_f32_block
+ * kernel; world > 1 adds a block-absmax pass and a max over the ranks of the
+ * ceil(n / 256) words -- ncclAllReduce(max) on "rccl" / "ar" / "a2a", else the
+ * ranks' words gathered by the engine's int32 allreduce (W / 256 of the
+ * bucket's bytes) -- and every engine carries the bucket through its int32
+ * reduce-scatter or allreduce ("a2a", "p2p", "ll", "mesh": the int32 allreduce).
+ * The mean and non-finite modes apply, the latter per block.  bf16 / fp16
+ * buckets, inccl_allreduce_f32_host and prepared ops refuse it (INCCL_ERR_ARG).
  * stream NULL = the communicator's stream.  dst may alias srcs[0].  A
  * communicator's calls (allreduce, reduce-scatter, any format) may come on any
  * stream: one on another stream than the previous call's waits for that call's
