@@ -44,6 +44,7 @@ SIGNATURES = {
     "inccl_absmax_f32": (_I, [_P, _I, _SZ, _P, _I, _P]),
     "inccl_block_absmax_f32": (_I, [_P, _I, _SZ, _P, _I, _P]),
     "inccl_reduce_f32_block": (_I, [_P, _I, _P, _SZ, _P, _I, _P]),
+    "inccl_reduce_f32_block16": (_I, [_P, _I, _P, _SZ, _P, _I, _P]),
     "inccl_stream_op_block": (_I, [_I, _I, _P, _I, _P, _SZ, _P, _SZ, _I, _P]),
     "inccl_checksum_q32": (_I, [_P, _SZ, _U64, _P, _I, _P]),
     "inccl_choose_scale": (_I, [_F, _I]),
@@ -73,6 +74,8 @@ SIGNATURES = {
     "inccl_comm_clear_error": (_I, [_P]),
     "inccl_comm_set_average": (_I, [_P, _I]),
     "inccl_comm_set_nonfinite": (_I, [_P, _I]),
+    "inccl_comm_set_wire": (_I, [_P, _I]),
+    "inccl_comm_wire": (_I, [_P]),
     "inccl_comm_set_stage_timing": (_I, [_P, _I]),
     "inccl_comm_stage_times": (_I, [_P, _P, _I, _P]),
     "inccl_reduce_scatter_f32": (_I, [_P, _P, _I, _P, _SZ, _I, _P]),

@@ -13,6 +13,7 @@
 
 #include "inccl_internal.h"
 #include "inccl_kernels.h"
+#include "inccl_scale_rule.h"
 
 /* ------------------------------------------------------------------ */
 /* errors                                                               */
@@ -120,7 +121,14 @@ int inccl_reduce_f32_block(const float *const *srcs_dev, int R, float *dst_dev, 
                            int flags, void *stream)
 {
     if (!srcs_dev) return inccl_set_error(INCCL_ERR_ARG, "srcs is NULL");
-    return kerr(inccl_k_block_fused((const void *const *)srcs_dev, R, dst_dev, n, words_out_dev, flags, R, 0, stream));
+    return kerr(inccl_k_block_fused((const void *const *)srcs_dev, R, dst_dev, n, words_out_dev, flags, R, 0, 0, stream));
+}
+
+int inccl_reduce_f32_block16(const float *const *srcs_dev, int R, float *dst_dev, size_t n, uint32_t *words_out_dev,
+                             int flags, void *stream)
+{
+    if (!srcs_dev) return inccl_set_error(INCCL_ERR_ARG, "srcs is NULL");
+    return kerr(inccl_k_block_fused((const void *const *)srcs_dev, R, dst_dev, n, words_out_dev, flags, R, 0, 1, stream));
 }
 
 int inccl_stream_op_block(int in_kind, int out_kind, const void *const *srcs_dev, int R, void *dst_dev, size_t n,
@@ -128,6 +136,9 @@ int inccl_stream_op_block(int in_kind, int out_kind, const void *const *srcs_dev
 {
     if (!srcs_dev) return inccl_set_error(INCCL_ERR_ARG, "srcs is NULL");
     if (scale_R < 0) return inccl_set_error(INCCL_ERR_ARG, "inccl_stream_op_block: scale_R %d is negative", scale_R);
+    if (out_kind == INCCL_KIND_P16 && (elem_base & 1))
+        return inccl_set_error(INCCL_ERR_ARG, "inccl_stream_op_block: F32 -> P16 at an odd elem_base %zu (a word holds "
+                               "elements 2j and 2j + 1 of the bucket)", elem_base);
     return kerr(inccl_k_stream_block(in_kind, out_kind, srcs_dev, R, dst_dev, n, words_dev,
                                      (elem_base + n + INCCL_BLOCK_ELEMS - 1) / INCCL_BLOCK_ELEMS, elem_base, scale_R, 0,
                                      stream));
@@ -885,6 +896,21 @@ int inccl_comm_set_nonfinite(struct inccl_communicator *comm, int mode)
     return 0;
 }
 
+int inccl_comm_set_wire(struct inccl_communicator *comm, int wire)
+{
+    if (!comm) return inccl_set_error(INCCL_ERR_ARG, "NULL communicator");
+    if (wire != INCCL_WIRE_Q32 && wire != INCCL_WIRE_P16)
+        return inccl_set_error(INCCL_ERR_ARG, "set_wire: unknown wire %d", wire);
+    comm->wire = wire;
+    return 0;
+}
+
+int inccl_comm_wire(struct inccl_communicator *comm)
+{
+    if (!comm) return inccl_set_error(INCCL_ERR_ARG, "NULL communicator");
+    return comm->wire;
+}
+
 int inccl_comm_clear_error(struct inccl_communicator *comm)
 {
     if (!comm) return inccl_set_error(INCCL_ERR_ARG, "comm is NULL");
@@ -981,7 +1007,11 @@ static int resolve_scale(struct inccl_communicator *c, int kind, const void *con
     sc->R = R * W;
     sc->blk = NULL;
     sc->nb = sc->blk_base = 0;
-    if (scale_exp == INCCL_SCALE_BLOCK) return resolve_block_scale(c, srcs, R, n, st, sc);
+    sc->p16 = 0;
+    if (scale_exp == INCCL_SCALE_BLOCK) {
+        sc->p16 = c->wire == INCCL_WIRE_P16;
+        return resolve_block_scale(c, srcs, R, n, st, sc);
+    }
     if (scale_exp != INCCL_SCALE_AUTO) {
         if (scale_exp < INCCL_SCALE_MIN || scale_exp > INCCL_SCALE_MAX)
             return inccl_set_error(INCCL_ERR_ARG, "scale_exp %d out of range", scale_exp);
@@ -1015,15 +1045,21 @@ static int resolve_scale(struct inccl_communicator *c, int kind, const void *con
 
 /* ---- the stages every sharded route is made of ---- */
 
-/* quantise + local sum of the R buckets of `kind` into q[0, n), zeros up to `total` */
+/* int32 wire words that carry n elements: one each, or two elements a word on
+ * the packed 16-bit wire (INCCL_WIRE_P16) */
+static size_t wire_words(const struct inccl_scale *sc, size_t n) { return sc->p16 ? (n + 1) / 2 : n; }
+
+/* quantise + local sum of the R buckets of `kind` into the wire words of
+ * elements [0, n) at q, zero words up to those of `total` elements */
 static int quant_sum(int kind, const void *const *srcs, int R, int32_t *q, size_t n, size_t total,
                      const struct inccl_scale *sc, hipStream_t st)
 {
-    const int rc = sc->blk ? kerr(inccl_k_stream_block(kind, INCCL_KIND_Q32, srcs, R, q, n, sc->blk, sc->nb,
-                                                       sc->blk_base, sc->R, 0, st))
+    const int rc = sc->blk ? kerr(inccl_k_stream_block(kind, sc->p16 ? INCCL_KIND_P16 : INCCL_KIND_Q32, srcs, R, q, n,
+                                                       sc->blk, sc->nb, sc->blk_base, sc->R, 0, st))
                            : kerr(inccl_k_stream(kind, INCCL_KIND_Q32, srcs, R, q, n, sc->k, sc->amax, sc->R, st));
     if (rc) return rc;
-    if (total > n) INCCL_HIP(hipMemsetAsync(q + n, 0, (total - n) * sizeof(int32_t), st));
+    const size_t nw = wire_words(sc, n), tw = wire_words(sc, total);
+    if (tw > nw) INCCL_HIP(hipMemsetAsync(q + nw, 0, (tw - nw) * sizeof(int32_t), st));
     return 0;
 }
 
@@ -1038,14 +1074,15 @@ static int stage_quant(struct inccl_communicator *c, int kind, const void *const
 }
 
 /* dst[0, n) = the reduced int32 partials q dequantised to `kind`; q[0] is
- * element `lo` of the piece the scale belongs to (per-block exponents) */
+ * element `lo` of the piece the scale belongs to (per-block exponents; on the
+ * packed wire the word that holds it) */
 static int stage_dequant(struct inccl_communicator *c, int kind, const int32_t *q, void *dst, size_t n, size_t lo,
                          const struct inccl_scale *sc, hipStream_t st)
 {
     const void *s1[1] = {q};
     const int si = stage_open(c, st);
-    const int rc = sc->blk ? kerr(inccl_k_stream_block(INCCL_KIND_Q32, kind, s1, 1, dst, n, sc->blk, sc->nb,
-                                                       sc->blk_base + lo, sc->R, c->out_shift, st))
+    const int rc = sc->blk ? kerr(inccl_k_stream_block(sc->p16 ? INCCL_KIND_P16 : INCCL_KIND_Q32, kind, s1, 1, dst, n,
+                                                       sc->blk, sc->nb, sc->blk_base + lo, sc->R, c->out_shift, st))
                            : kerr(inccl_k_stream_s(INCCL_KIND_Q32, kind, s1, 1, dst, n, sc->k, sc->amax, sc->R,
                                                    c->out_shift, st));
     if (rc) return rc;
@@ -1062,16 +1099,21 @@ static int allreduce_via_q32(struct inccl_communicator *c, int kind, const void 
 {
     int rc = inccl_ws_claim(c, st);
     if (rc) return rc;
-    rc = inccl_ensure_dev(&c->d_q32, &c->d_q32_bytes, n * sizeof(int32_t));
+    const size_t nw = wire_words(sc, n);
+    /* the in-process transport sums the ranks' words into the head of its own
+     * d_q32 while its peers still read theirs (inccl_local_allreduce_q32): the
+     * words it publishes live behind that scratch, 256-B aligned */
+    const size_t head = c->group->transport == INCCL_TRANSPORT_LOCAL ? (nw + 63) / 64 * 64 : 0;
+    rc = inccl_ensure_dev(&c->d_q32, &c->d_q32_bytes, (head + nw) * sizeof(int32_t));
     if (rc) return rc;
-    int32_t *q = (int32_t *)c->d_q32;
+    int32_t *q = (int32_t *)c->d_q32 + head;
     rc = stage_quant(c, kind, srcs, R, q, n, n, sc, st);
     if (rc) return rc;
     const int si = stage_open(c, st);
-    rc = inccl_tp_allreduce_q32(c, q, q, n, st);
+    rc = inccl_tp_allreduce_q32(c, q, q, nw, st);
     if (rc) return rc;
     stage_close(c, si, st, INCCL_STAGE_AR);
-    return stage_dequant(c, kind, q + lo, dst, cnt, lo, sc, st);
+    return stage_dequant(c, kind, q + (sc->p16 ? lo / 2 : lo), dst, cnt, lo, sc, st);
 }
 
 /* Variant B, fp32 only: quant + local sum -> grouped
@@ -1208,12 +1250,29 @@ static int allreduce_rsag(struct inccl_communicator *c, int kind, const void *co
 static const char *const kind_names[] = {"f32", "", "", "bf16", "f16"};
 
 /* INCCL_SCALE_BLOCK on the FUSED route: one HBM pass, no words pass (the only
- * rank's words are the agreed ones and stay in the kernel's registers) */
+ * rank's words are the agreed ones and stay in the kernel's registers).  On the
+ * packed wire the kernel takes the 16-bit lanes' exponent and clamp, so that one
+ * rank gives what N ranks would give. */
 static int block_fused(struct inccl_communicator *c, const void *const *srcs, int R, void *dst, size_t n,
                        hipStream_t st)
 {
     const int flags = c->nonfinite == INCCL_NONFINITE_NAN ? INCCL_ABSMAX_FLAG_NONFINITE : 0;
-    return kerr(inccl_k_block_fused(srcs, R, dst, n, NULL, flags, R * c->group->world_size, c->out_shift, st));
+    return kerr(inccl_k_block_fused(srcs, R, dst, n, NULL, flags, R * c->group->world_size, c->out_shift,
+                                    c->wire == INCCL_WIRE_P16, st));
+}
+
+/* The route of an INCCL_SCALE_BLOCK call: inccl_route_block, then on the packed
+ * wire inccl_route_packed; more contributors than a 16-bit lane holds are refused */
+static int block_route(struct inccl_communicator *c, int R, size_t n, enum inccl_route *route)
+{
+    *route = inccl_route_block(*route);
+    if (c->wire != INCCL_WIRE_P16) return 0;
+    const int W = c->group->world_size;
+    if ((long long)R * W > INCCL_P16_LANE_MAX)
+        return inccl_set_error(INCCL_ERR_ARG, "INCCL_WIRE_P16: %lld contributors exceed a 16-bit lane's %d",
+                               (long long)R * W, INCCL_P16_LANE_MAX);
+    *route = inccl_route_packed(*route, n, W);
+    return 0;
 }
 
 /* The allreduce of kind F32, BF16 or F16 buckets.  The int32 partial sums
@@ -1236,12 +1295,14 @@ static int allreduce_body(struct inccl_communicator *c, int kind, const void *co
     enum inccl_route route =
         inccl_route_of(INCCL_OP_ALLREDUCE, kind, c->group->transport, c->engine, c->group->world_size,
                        c->force_sharded, c->mesh_rs, n, c->rccl_ar_bytes, c->ll_max_bytes);
+    int rc;
     if (block) {
-        route = inccl_route_block(route);
+        rc = block_route(c, R, n, &route);
+        if (rc) return rc;
         if (route == INCCL_ROUTE_FUSED) return block_fused(c, srcs, R, dst, n, st);
     }
     struct inccl_scale sc;
-    int rc = resolve_scale(c, kind, srcs, R, n, scale_exp, st, &sc);
+    rc = resolve_scale(c, kind, srcs, R, n, scale_exp, st, &sc);
     if (rc) return rc;
     switch (route) {
         case INCCL_ROUTE_FUSED:   /* one HBM pass: quant + sum + dequant */
@@ -1334,12 +1395,14 @@ static int reduce_scatter_body(struct inccl_communicator *c, int kind, const voi
     enum inccl_route route =
         inccl_route_of(INCCL_OP_REDUCE_SCATTER, kind, c->group->transport, c->engine, W, c->force_sharded, c->mesh_rs,
                        n, c->rccl_ar_bytes, c->ll_max_bytes);
+    int rc;
     if (scale_exp == INCCL_SCALE_BLOCK) {
-        route = inccl_route_block(route);
+        rc = block_route(c, R, n, &route);
+        if (rc) return rc;
         if (route == INCCL_ROUTE_FUSED) return block_fused(c, srcs, R, dst, n, st);
     }
     struct inccl_scale sc;
-    int rc = resolve_scale(c, kind, srcs, R, n, scale_exp, st, &sc);
+    rc = resolve_scale(c, kind, srcs, R, n, scale_exp, st, &sc);
     if (rc) return rc;
     switch (route) {
         case INCCL_ROUTE_FUSED:   /* one HBM pass */
@@ -1347,13 +1410,15 @@ static int reduce_scatter_body(struct inccl_communicator *c, int kind, const voi
         case INCCL_ROUTE_RS: {    /* quant + local sum -> int32 reduce-scatter -> dequantise the shard */
             rc = inccl_ws_claim(c, st);
             if (rc) return rc;
-            rc = inccl_ensure_dev(&c->d_q32, &c->d_q32_bytes, (n + shard) * sizeof(int32_t));
+            /* the packed wire comes here with an even shard only (inccl_route_packed) */
+            const size_t nw = wire_words(&sc, n), sw = wire_words(&sc, shard);
+            rc = inccl_ensure_dev(&c->d_q32, &c->d_q32_bytes, (nw + sw) * sizeof(int32_t));
             if (rc) return rc;
-            int32_t *qsend = (int32_t *)c->d_q32, *qrecv = qsend + n;
+            int32_t *qsend = (int32_t *)c->d_q32, *qrecv = qsend + nw;
             rc = stage_quant(c, kind, srcs, R, qsend, n, n, &sc, st);
             if (rc) return rc;
             const int si = stage_open(c, st);
-            rc = inccl_tp_reduce_scatter_q32(c, qsend, qrecv, shard, st);
+            rc = inccl_tp_reduce_scatter_q32(c, qsend, qrecv, sw, st);
             if (rc) return rc;
             stage_close(c, si, st, INCCL_STAGE_RS);
             return stage_dequant(c, kind, qrecv, dst, shard, (size_t)me * shard, &sc, st);

@@ -18,6 +18,9 @@
 //                                quads it already holds; (R + 1) * 4 * n bytes
 //                                (+ n / 64 when the words are written out)
 //   k_block_fused_elem<R>        the same on buckets that are not 16-B aligned
+//                                (both with P16: the exponent and the clamp of
+//                                packed 16-bit lanes, inccl_pack.hip, so that
+//                                world 1 gives what N ranks would give)
 //   k_block_absmax<R, NF>        the words of R local buckets: one wave per block
 //                                and step, plain stores, overwrites
 //   k_stream_block<IN, OUT, R>   F32 -> Q32 (quantise + local sum) and Q32 -> F32
@@ -32,9 +35,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "inccl_kernels.h"
-#include "inccl_scale_rule.h"
-#include "inccl_stream.h"
+#include "inccl_block.h"
 
 namespace {
 
@@ -66,23 +67,9 @@ __device__ __forceinline__ uint32_t amax_quad(u32x4 x)
     return max(max(abs_bits<NF>(x.x), abs_bits<NF>(x.y)), max(abs_bits<NF>(x.z), abs_bits<NF>(x.w)));
 }
 
-// one block's multipliers from its word: 2^k_b to quantise, 2^-(k_b + out_shift)
-// to dequantise -- NaN when the word carries bit 31 (that block's results are NaN)
-struct BlockMul {
-    float scale, inv;
-};
-__device__ __forceinline__ BlockMul block_mul(uint32_t word, int scale_R, int out_shift)
-{
-    const int k = inccl_scale_of_word(word, scale_R);
-    BlockMul b;
-    b.scale = pow2f(k);
-    b.inv = (word >> 31) ? __builtin_nanf("") : pow2f(-k - out_shift);
-    return b;
-}
-
 __device__ __forceinline__ uint32_t fused1(uint32_t acc, float inv) { return store_xform<F32>(acc, inv); }
 
-template <int R, bool NF, int BLOCK, int U>
+template <int R, bool NF, bool P16, int BLOCK, int U>
 __global__ __launch_bounds__(BLOCK) void k_stream_block_fused(SrcPtrs src, void* __restrict__ dst, int64_t n,
                                                               uint32_t* __restrict__ words, int scale_R,
                                                               int out_shift)
@@ -92,6 +79,7 @@ __global__ __launch_bounds__(BLOCK) void k_stream_block_fused(SrcPtrs src, void*
     const int64_t nq = ((n + 255) >> 8) << 6;         // quads of whole blocks: a wave for every block
     const int64_t tile = (int64_t)BLOCK * U;
     const int lane = threadIdx.x & 63;
+    const int L = P16 ? inccl_p16_clamp(scale_R) : 0;   // the packed lanes' clamp, unused otherwise
     u32x4* __restrict__ out = reinterpret_cast<u32x4*>(dst);
     uint32_t* __restrict__ out1 = reinterpret_cast<uint32_t*>(dst);
 
@@ -133,15 +121,15 @@ __global__ __launch_bounds__(BLOCK) void k_stream_block_fused(SrcPtrs src, void*
             }
             // the block's word, wave-uniform: the exponent is resolved once per wave
             const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max_u32(m));
-            const BlockMul bm = block_mul(w, scale_R, out_shift);
+            const BlockMul bm = block_mul<P16>(w, scale_R, out_shift);
             if (words != nullptr && lane == 0) words[i >> 6] = w;
             u32x4 acc = {0u, 0u, 0u, 0u};
 #pragma unroll
             for (int r = 0; r < R; ++r) {
-                acc.x += quant1(__uint_as_float(v[r][u].x), bm.scale);
-                acc.y += quant1(__uint_as_float(v[r][u].y), bm.scale);
-                acc.z += quant1(__uint_as_float(v[r][u].z), bm.scale);
-                acc.w += quant1(__uint_as_float(v[r][u].w), bm.scale);
+                acc.x += quantb<P16>(__uint_as_float(v[r][u].x), bm.scale, L);
+                acc.y += quantb<P16>(__uint_as_float(v[r][u].y), bm.scale, L);
+                acc.z += quantb<P16>(__uint_as_float(v[r][u].z), bm.scale, L);
+                acc.w += quantb<P16>(__uint_as_float(v[r][u].w), bm.scale, L);
             }
             u32x4 o;
             o.x = fused1(acc.x, bm.inv);
@@ -158,7 +146,7 @@ __global__ __launch_bounds__(BLOCK) void k_stream_block_fused(SrcPtrs src, void*
                     if (j < tail) {
                         uint32_t a = 0;
 #pragma unroll
-                        for (int r = 0; r < R; ++r) a += quant1(__uint_as_float(t[r][j]), bm.scale);
+                        for (int r = 0; r < R; ++r) a += quantb<P16>(__uint_as_float(t[r][j]), bm.scale, L);
                         out1[n4 * 4 + j] = fused1(a, bm.inv);
                     }
             }
@@ -170,12 +158,13 @@ constexpr int kBlkWaves = kBlock / 64;   // waves = blocks per workgroup and ste
 
 // the fused kernel per element: lane t of the block's wave takes elements
 // 256 b + t + 64 j, j < 4 (coalesced dword accesses)
-template <int R, bool NF>
+template <int R, bool NF, bool P16>
 __global__ __launch_bounds__(kBlock) void k_block_fused_elem(SrcPtrs src, void* __restrict__ dst, int64_t n,
                                                              uint32_t* __restrict__ words, int scale_R, int out_shift)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t nb = (n + 255) >> 8;
+    const int L = P16 ? inccl_p16_clamp(scale_R) : 0;
     uint32_t* __restrict__ out = reinterpret_cast<uint32_t*>(dst);
     for (int64_t b = (int64_t)blockIdx.x * kBlkWaves + wave; b < nb; b += (int64_t)gridDim.x * kBlkWaves) {
         uint32_t x[R][4];
@@ -195,7 +184,7 @@ __global__ __launch_bounds__(kBlock) void k_block_fused_elem(SrcPtrs src, void* 
                 m = m > a ? m : a;
             }
         const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max_u32(m));
-        const BlockMul bm = block_mul(w, scale_R, out_shift);
+        const BlockMul bm = block_mul<P16>(w, scale_R, out_shift);
         if (words != nullptr && lane == 0) words[b] = w;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -203,7 +192,7 @@ __global__ __launch_bounds__(kBlock) void k_block_fused_elem(SrcPtrs src, void* 
             if (e < n) {
                 uint32_t a = 0;
 #pragma unroll
-                for (int r = 0; r < R; ++r) a += quant1(__uint_as_float(x[r][j]), bm.scale);
+                for (int r = 0; r < R; ++r) a += quantb<P16>(__uint_as_float(x[r][j]), bm.scale, L);
                 out[e] = fused1(a, bm.inv);
             }
         }
@@ -253,12 +242,6 @@ __global__ __launch_bounds__(kBlock) void k_block_absmax(SrcPtrs src, int64_t n,
         m = wave_max_u32(m);
         if (lane == 0) words[b] = m;
     }
-}
-
-// the word of the bucket's block `blk`, clamped to the words the caller holds
-__device__ __forceinline__ uint32_t word_at(const uint32_t* __restrict__ words, int64_t blk, int64_t nb)
-{
-    return words[blk < nb ? blk : nb - 1];
 }
 
 // out = OUT(sum_r IN(src_r)) over quads, <F32, Q32> or <Q32, F32>; quad i holds
@@ -325,41 +308,7 @@ __global__ __launch_bounds__(kBlock) void k_words_max(const uint32_t* __restrict
 // ---------------------------------------------------------------------------
 // host-side dispatch
 // ---------------------------------------------------------------------------
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-int grid_cap()
-{
-    static int cus = 0;
-    if (cus == 0) {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) == hipSuccess &&
-            hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
-            cus = v;
-        else
-            cus = 256;
-    }
-    return cus * 8;
-}
-
-int grid_of(int64_t items, int per_group)
-{
-    const int64_t g = (items + per_group - 1) / per_group, cap = grid_cap();
-    return (int)(g < 1 ? 1 : (g < cap ? g : cap));
-}
-
-int fill_srcs(const void* const* srcs, int R, SrcPtrs* s, bool* vec)
-{
-    if (srcs == nullptr || R < 1 || R > kMaxR) return INCCL_ERR_ARG;
-    *s = SrcPtrs{};
-    for (int r = 0; r < R; ++r) {
-        if (srcs[r] == nullptr) return INCCL_ERR_ARG;
-        s->p[r] = srcs[r];
-        *vec = *vec && aligned16(srcs[r]);
-    }
-    return 0;
-}
-
-template <int R, bool NF>
+template <int R, bool NF, bool P16>
 void launch_fused(const SrcPtrs& s, void* dst, int64_t n, uint32_t* words, int scale_R, int out_shift, bool vec,
                   hipStream_t st)
 {
@@ -369,10 +318,10 @@ void launch_fused(const SrcPtrs& s, void* dst, int64_t n, uint32_t* words, int s
         // one workgroup per tile, as the single-scale fused kernel
         const int64_t tiles = (nb * 64 + (int64_t)B * U - 1) / ((int64_t)B * U);
         const int grid = (int)(tiles < 0x7fffffff ? tiles : 0x7fffffff);
-        hipLaunchKernelGGL((k_stream_block_fused<R, NF, B, U>), dim3(grid), dim3(B), 0, st, s, dst, n, words, scale_R,
+        hipLaunchKernelGGL((k_stream_block_fused<R, NF, P16, B, U>), dim3(grid), dim3(B), 0, st, s, dst, n, words, scale_R,
                            out_shift);
     } else {
-        hipLaunchKernelGGL((k_block_fused_elem<R, NF>), dim3(grid_of(nb, kBlkWaves)), dim3(kBlock), 0, st, s, dst, n,
+        hipLaunchKernelGGL((k_block_fused_elem<R, NF, P16>), dim3(grid_of(nb, kBlkWaves)), dim3(kBlock), 0, st, s, dst, n,
                            words, scale_R, out_shift);
     }
 }
@@ -402,18 +351,6 @@ void launch_stream(const SrcPtrs& s, void* dst, int64_t n, const uint32_t* words
                            dst, done, n, words, nb, elem_base, scale_R, out_shift);
 }
 
-#define INCCL_R_SWITCH(R, CALL) \
-    switch (R) {                \
-        case 1: CALL(1); break; \
-        case 2: CALL(2); break; \
-        case 3: CALL(3); break; \
-        case 4: CALL(4); break; \
-        case 5: CALL(5); break; \
-        case 6: CALL(6); break; \
-        case 7: CALL(7); break; \
-        default: CALL(8); break; \
-    }
-
 }  // namespace
 
 extern "C" {
@@ -435,21 +372,28 @@ int inccl_k_block_absmax(const void* const* srcs, int R, size_t n, uint32_t* wor
 }
 
 int inccl_k_block_fused(const void* const* srcs, int R, void* dst, size_t n, uint32_t* words_out_dev, int flags,
-                        int scale_R, int out_shift, void* stream)
+                        int scale_R, int out_shift, int p16, void* stream)
 {
     SrcPtrs s;
     bool vec = aligned16(dst);
     if (fill_srcs(srcs, R, &s, &vec) || (flags & ~INCCL_ABSMAX_FLAG_NONFINITE) || (dst == nullptr && n > 0) ||
         out_shift < 0 || out_shift > 8)
         return INCCL_ERR_ARG;
-    if (n == 0) return 0;
     if (scale_R <= 0) scale_R = R;
+    if (p16 && scale_R > INCCL_P16_LANE_MAX) return INCCL_ERR_ARG;
+    if (n == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
+#define INCCL_FUSED(RR, NF, P)                                                                            \
+    launch_fused<RR, NF, P>(s, dst, (int64_t)n, words_out_dev, scale_R, out_shift, vec, st)
 #define INCCL_CALL(RR)                                                                                    \
-    if (flags) launch_fused<RR, true>(s, dst, (int64_t)n, words_out_dev, scale_R, out_shift, vec, st);   \
-    else launch_fused<RR, false>(s, dst, (int64_t)n, words_out_dev, scale_R, out_shift, vec, st)
+    if (p16) {                                                                                            \
+        if (flags) INCCL_FUSED(RR, true, true);                                                           \
+        else INCCL_FUSED(RR, false, true);                                                                \
+    } else if (flags) INCCL_FUSED(RR, true, false);                                                       \
+    else INCCL_FUSED(RR, false, false)
     INCCL_R_SWITCH(R, INCCL_CALL)
 #undef INCCL_CALL
+#undef INCCL_FUSED
     return (int)hipGetLastError();
 }
 
@@ -457,6 +401,9 @@ int inccl_k_stream_block(int in_kind, int out_kind, const void* const* srcs, int
                          const uint32_t* words_dev, size_t nb, size_t elem_base, int scale_R, int out_shift,
                          void* stream)
 {
+    if (in_kind == P16 || out_kind == P16)   // packed 16-bit lanes: inccl_pack.hip
+        return inccl_k_stream_block16(in_kind, out_kind, srcs, R, dst, n, words_dev, nb, elem_base, scale_R, out_shift,
+                                      stream);
     SrcPtrs s;
     bool vec = aligned16(dst);
     const bool quant = in_kind == F32 && out_kind == Q32, deq = in_kind == Q32 && out_kind == F32;

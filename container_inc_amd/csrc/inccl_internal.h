@@ -80,6 +80,7 @@ struct inccl_communicator {
     int engine;                  /* INCCL_ENGINE_* */
     int out_shift;               /* log2(world) when results are averaged (inccl_comm_set_average), else 0 */
     int nonfinite;               /* INCCL_NONFINITE_* (inccl_comm_set_nonfinite) */
+    int wire;                    /* INCCL_WIRE_* (inccl_comm_set_wire): what INCCL_SCALE_BLOCK calls exchange */
     size_t p2p_cap;              /* elements per buffer */
     int32_t *p2p_part;           /* this rank's quantised partial sums (W * shard) */
     float *p2p_res;              /* this rank's dequantised shard lives at rank * shard */
@@ -166,13 +167,16 @@ int inccl_rccl_alltoall_q32(struct inccl_communicator *c, const int32_t *send, i
  * summed over the whole group.  INCCL_SCALE_BLOCK: blk points at the agreed word
  * of the bucket's block 0 (nb of them; k and amax unused) and blk_base is where
  * the piece this scale is handed to starts in the bucket, in elements.  Only
- * the stage helpers of api.c take such a scale (inccl_route_block). */
+ * the stage helpers of api.c take such a scale (inccl_route_block).  p16: the
+ * blocks travel as packed 16-bit lanes (INCCL_WIRE_P16), two elements an int32
+ * wire word (inccl_route_packed). */
 struct inccl_scale {
     int k;
     const uint32_t *amax;
     int R;
     const uint32_t *blk;
     size_t nb, blk_base;
+    int p16;
 };
 
 /* p2p engine (p2p.c): allreduce and reduce-scatter of kind F32 / BF16 / F16

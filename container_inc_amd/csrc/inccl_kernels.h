@@ -30,10 +30,17 @@ int inccl_k_checksum(const int32_t *q, size_t n, uint64_t index_base, uint32_t *
  *                 kernel for scale_R contributors; words_out (NULL ok) receives the words
  *   stream_block  F32 -> Q32 or Q32 -> F32 at the agreed words: element i is element elem_base + i of
  *                 the bucket whose block 0 words_dev points at; a block index past nb - 1 reads word nb - 1
- *   words_max     out[b] = max_j rows[j * nb + b] (unsigned) */
+ *   words_max     out[b] = max_j rows[j * nb + b] (unsigned)
+ * Packed 16-bit lanes (INCCL_KIND_P16; inccl_pack.hip): block_fused with p16 != 0 takes the lanes'
+ * exponent and clamp; stream_block also takes F32 -> P16 (dst: ceil(n / 2) words, elem_base even) and
+ * P16 -> F32 (n: elements of dst; srcs point at the word that holds element elem_base) and hands them
+ * to stream_block16.  scale_R above INCCL_P16_LANE_MAX is INCCL_ERR_ARG. */
 int inccl_k_block_absmax(const void *const *srcs, int R, size_t n, uint32_t *words_dev, int flags, void *stream);
 int inccl_k_block_fused(const void *const *srcs, int R, void *dst, size_t n, uint32_t *words_out_dev, int flags,
-                        int scale_R, int out_shift, void *stream);
+                        int scale_R, int out_shift, int p16, void *stream);
+int inccl_k_stream_block16(int in_kind, int out_kind, const void *const *srcs, int R, void *dst, size_t n,
+                           const uint32_t *words_dev, size_t nb, size_t elem_base, int scale_R, int out_shift,
+                           void *stream);
 int inccl_k_stream_block(int in_kind, int out_kind, const void *const *srcs, int R, void *dst, size_t n,
                          const uint32_t *words_dev, size_t nb, size_t elem_base, int scale_R, int out_shift,
                          void *stream);

@@ -103,4 +103,23 @@ static inline enum inccl_route inccl_route_block(enum inccl_route route)
     }
 }
 
+/* The route an INCCL_SCALE_BLOCK call takes on the packed 16-bit wire
+ * (INCCL_WIRE_P16), applied after inccl_route_block.  Two elements share an
+ * int32 wire word and a word cannot be dequantised before every rank's
+ * contribution is in it, so:
+ *  - RSAG becomes AR: the reduced words are what travels, both halves of the
+ *    exchange then move 2 bytes an element (a gather of dequantised fp32 shards
+ *    would move 4), and `chunks` is ignored;
+ *  - RS stays while a shard of n / W elements is whole words, else AR_SHARD,
+ *    whose dequantise may start at a word's high lane;
+ *  - FUSED, AR and AR_SHARD are unchanged. */
+static inline enum inccl_route inccl_route_packed(enum inccl_route route, size_t n, int W)
+{
+    switch (route) {
+        case INCCL_ROUTE_RSAG: return INCCL_ROUTE_AR;
+        case INCCL_ROUTE_RS: return (n / (size_t)W) % 2 ? INCCL_ROUTE_AR_SHARD : INCCL_ROUTE_RS;
+        default: return route;
+    }
+}
+
 #endif

@@ -40,4 +40,19 @@ INCCL_HD int inccl_scale_of_word(uint32_t word, int R)
     return k;
 }
 
+/* Packed 16-bit lanes (INCCL_KIND_P16): 16 bits less than the 32-bit rule, so
+ * that R contributions of |q| <= ceil(2^14 / R) sum inside a signed 16-bit
+ * lane; a zero block gets INCCL_SCALE_MAX - 16. */
+INCCL_HD int inccl_p16_scale_of_word(uint32_t word, int R)
+{
+    const int k = inccl_scale_of_word(word, R) - 16;
+    return k < INCCL_SCALE_MIN ? INCCL_SCALE_MIN : k;
+}
+
+/* the largest contribution one of R contributors may add to a lane: the clamp
+ * binds only where the exponent was clamped at INCCL_SCALE_MIN and for +-Inf,
+ * and keeps a lane's sum inside [-32767, 32767] whatever the inputs */
+#define INCCL_P16_LANE_MAX 32767
+INCCL_HD int inccl_p16_clamp(int R) { return INCCL_P16_LANE_MAX / (R > 0 ? R : 1); }
+
 #endif

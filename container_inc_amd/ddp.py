@@ -28,6 +28,9 @@ parameters whose gradients differ by orders of magnitude, and under
 gain next to an embedding row keeps few or no significant bits).  The mean and
 the non-finite mode apply alike, the latter per block: only the blocks that
 held a NaN or +-Inf come out NaN.  A bf16 / fp16 bucket in this mode raises.
+``wire_bits=16`` with it exchanges packed 16-bit lanes (``Communicator.set_wire``,
+``inccl_comm_set_wire``): half the exchanged bytes at 16 bits less precision per
+block, for 2-16 contributors; 32 (the default) is one int32 per element.
 
 fp32, bf16 and fp16 CUDA buckets are accepted (bf16 / fp16 through
 ``inccl_allreduce_bf16`` / ``_f16``: the same int32 sums, the result rounded to
@@ -66,6 +69,8 @@ class HookState:
     folded: bool | None = None   # the mean comes out of the dequantise stage (inccl_comm_set_average)
     propagate_nonfinite: bool = True   # NaN / +-Inf anywhere -> the bucket is NaN (inccl_comm_set_nonfinite)
     _nonfinite_set: bool = False
+    _wire_set: bool = False
+    wire_bits: int = 32          # 16: SCALE_BLOCK buckets travel as packed 16-bit lanes (inccl_comm_set_wire)
 
     def fold_average(self) -> bool:
         """Once: let the engine return the mean (power-of-two worlds: 2^-log2 W is
@@ -88,6 +93,16 @@ class HookState:
             self._nonfinite_set = True
             if hasattr(self.comm, "set_nonfinite"):
                 self.comm.set_nonfinite(self.propagate_nonfinite)
+
+    def apply_wire(self) -> None:
+        """Once: the communicator's wire for per-block scaled buckets."""
+        if self.wire_bits not in (16, 32):
+            raise IncclError(f"inccl hook: wire_bits={self.wire_bits!r} is not a wire; 32 (one int32 per element) "
+                             f"or 16 (packed 16-bit lanes)")
+        if not self._wire_set:
+            self._wire_set = True
+            if hasattr(self.comm, "set_wire"):
+                self.comm.set_wire(inccl.WIRE_P16 if self.wire_bits == 16 else inccl.WIRE_Q32)
 
     def check_format(self, dtype) -> None:
         """Per-block scaling serves fp32 buckets only: say so here, by name."""
@@ -119,6 +134,7 @@ def allreduce_hook(state: HookState, bucket):
     state.check_format(buf.dtype)
     reduce = getattr(state.comm, name)
     state.apply_nonfinite()
+    state.apply_wire()
     w = state.world_size
     divide = state.average and w > 1 and not state.fold_average()
     if not buf.is_cuda:   # reaches the communicator, which refuses it ("must live on the GPU")
@@ -170,10 +186,11 @@ def communicator_from_env(port_offset: int = 17, device: int | None = None, engi
     return comm
 
 
-def register(ddp_model, comm, scale_exp: int = inccl.SCALE_AUTO, average: bool = True) -> HookState:
+def register(ddp_model, comm, scale_exp: int = inccl.SCALE_AUTO, average: bool = True, wire_bits: int = 32) -> HookState:
     """Route every gradient bucket of ``ddp_model`` through ``comm``; returns the hook
     state.  ``scale_exp``: a fixed exponent, ``SCALE_AUTO`` (one per bucket) or
-    ``SCALE_BLOCK`` (one per 256-element block, fp32 buckets)."""
-    state = HookState(comm=comm, scale_exp=scale_exp, average=average)
+    ``SCALE_BLOCK`` (one per 256-element block, fp32 buckets; ``wire_bits=16``:
+    exchanged as packed 16-bit lanes)."""
+    state = HookState(comm=comm, scale_exp=scale_exp, average=average, wire_bits=wire_bits)
     ddp_model.register_comm_hook(state, allreduce_hook)
     return state

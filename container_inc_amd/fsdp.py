@@ -24,7 +24,8 @@ use without further synchronisation.  fp32, bf16 and fp16 gradients.
 ``register(..., scale_exp=inccl.SCALE_BLOCK)`` (fp32 gradients only) scales
 every 256-element block of the unsharded gradient on its own, shards included:
 a shard is dequantised at the exponents of the blocks it lies in, wherever it
-starts.  A bf16 / fp16 gradient in this mode raises.
+starts.  A bf16 / fp16 gradient in this mode raises.  ``wire_bits=16`` with it
+exchanges packed 16-bit lanes (``inccl_comm_set_wire``), as in the DDP hook.
 """
 from __future__ import annotations
 
@@ -38,6 +39,7 @@ def _check(state: HookState, grad):
         raise IncclError(f"inccl FSDP hook: fp32, bf16 or fp16 gradients only, got {grad.dtype}")
     state.check_format(grad.dtype)
     state.apply_nonfinite()
+    state.apply_wire()
     w = state.world_size
     return w, state.average and w > 1 and not state.fold_average()
 

@@ -21,6 +21,8 @@ import numpy as np
 from ._lib import IncclError, check, load
 
 KIND_F32, KIND_Q32, KIND_Q32BE, KIND_BF16, KIND_F16 = 0, 1, 2, 3, 4
+KIND_P16 = 5                     # inccl_amd.h INCCL_KIND_P16: packed 16-bit lanes, two elements an int32 word
+WIRE_Q32, WIRE_P16 = 0, 1        # inccl_amd.h INCCL_WIRE_*: what SCALE_BLOCK calls of a communicator exchange
 SCALE_MIN, SCALE_MAX, SCALE_AUTO = -64, 64, 0x7FFFFFFF
 SCALE_BLOCK = 0x7FFFFFFE         # inccl_amd.h INCCL_SCALE_BLOCK: one auto exponent per BLOCK_ELEMS elements (fp32)
 BLOCK_ELEMS = 256
@@ -75,7 +77,7 @@ def _check_scale(k: int) -> int:
 
 
 _TORCH_KIND = {KIND_F32: "float32", KIND_Q32: "int32", KIND_Q32BE: "int32", KIND_BF16: "bfloat16",
-               KIND_F16: "float16"}
+               KIND_F16: "float16", KIND_P16: "int32"}
 
 
 def stream_op(in_kind: int, out_kind: int, srcs, out=None, scale_exp: int = 0, n: int | None = None,
@@ -302,11 +304,30 @@ def reduce_f32_block(srcs, out=None, words=None, nonfinite_flag: bool = False, s
     return out
 
 
+def reduce_f32_block16(srcs, out=None, words=None, nonfinite_flag: bool = False, stream=None):
+    """``reduce_f32_block`` at the semantics of packed 16-bit lanes
+    (inccl_reduce_f32_block16): what the WIRE_P16 exchange of len(srcs) ranks gives."""
+    torch = _torch()
+    srcs = list(srcs)
+    n = srcs[0].numel()
+    ptrs = [_dev_ptr(s, torch.float32, f"srcs[{i}]", n) for i, s in enumerate(srcs)]
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device=srcs[0].device)
+    wptr = None if words is None else _dev_ptr(words, torch.int32, "words", _nblocks(n))
+    rc = load().inccl_reduce_f32_block16(_ptr_array(ptrs), len(ptrs), _dev_ptr(out, torch.float32, "out", n), n, wptr,
+                                         ABSMAX_FLAG_NONFINITE if nonfinite_flag else 0, _stream_handle(stream))
+    check(rc, "inccl_reduce_f32_block16")
+    return out
+
+
 def stream_op_block(in_kind: int, out_kind: int, srcs, words, out=None, elem_base: int = 0, scale_R: int = 0,
                     n: int | None = None, stream=None):
     """``stream_op`` F32 -> Q32 or Q32 -> F32 at agreed per-block words
     (inccl_stream_op_block): ``words[0]`` is the word of the bucket's block 0 and
-    element i of the call is element ``elem_base + i`` of that bucket."""
+    element i of the call is element ``elem_base + i`` of that bucket.  Also
+    F32 -> P16 (``out``: ceil(n / 2) int32 words; an even ``elem_base``) and
+    P16 -> F32, whose ``n`` counts the fp32 elements of ``out`` (default: every
+    lane of the sources, less the skipped low lane of an odd ``elem_base``)."""
     torch = _torch()
     srcs = list(srcs)
     if len(srcs) < 1 or len(srcs) > MAX_LOCAL_INPUTS:
@@ -314,14 +335,18 @@ def stream_op_block(in_kind: int, out_kind: int, srcs, words, out=None, elem_bas
     if elem_base < 0:
         raise ValueError(f"elem_base {elem_base} is negative")
     in_dt, out_dt = getattr(torch, _TORCH_KIND[in_kind]), getattr(torch, _TORCH_KIND[out_kind])
+    odd = int(elem_base) & 1
     if n is None:
-        n = srcs[0].numel()
-    ptrs = [_dev_ptr(s, in_dt, f"srcs[{i}]", n) for i, s in enumerate(srcs)]
+        n = 2 * srcs[0].numel() - odd if in_kind == KIND_P16 else srcs[0].numel()
+    n_in = (odd + n + 1) // 2 if in_kind == KIND_P16 else n      # a packed side counts int32 words
+    n_out = (n + 1) // 2 if out_kind == KIND_P16 else n
+    ptrs = [_dev_ptr(s, in_dt, f"srcs[{i}]", n_in) for i, s in enumerate(srcs)]
     if out is None:
-        out = torch.empty(n, dtype=out_dt, device=srcs[0].device)
+        out = torch.empty(n_out, dtype=out_dt, device=srcs[0].device)
     wptr = _dev_ptr(words, torch.int32, "words", _nblocks(int(elem_base) + n))
-    rc = load().inccl_stream_op_block(in_kind, out_kind, _ptr_array(ptrs), len(ptrs), _dev_ptr(out, out_dt, "out", n), n,
-                                      wptr, int(elem_base), int(scale_R), _stream_handle(stream))
+    rc = load().inccl_stream_op_block(in_kind, out_kind, _ptr_array(ptrs), len(ptrs),
+                                      _dev_ptr(out, out_dt, "out", n_out), n, wptr, int(elem_base), int(scale_R),
+                                      _stream_handle(stream))
     check(rc, "inccl_stream_op_block")
     return out
 
@@ -464,6 +489,20 @@ class Communicator:
         loss scaler needs to see; False restores the quantiser's spec (NaN -> 0,
         +-Inf saturates).  Set it alike on every rank."""
         check(load().inccl_comm_set_nonfinite(self.handle, 1 if propagate else 0), "inccl_comm_set_nonfinite")
+
+    def set_wire(self, wire: int) -> None:
+        """WIRE_P16: the SCALE_BLOCK calls of allreduce_f32 and reduce_scatter
+        exchange packed 16-bit lanes, half the bytes of WIRE_Q32 (the default), at
+        16 bits less precision per block -- meant for 2-16 contributors
+        (inccl_comm_set_wire).  Set it alike on every rank."""
+        check(load().inccl_comm_set_wire(self.handle, int(wire)), "inccl_comm_set_wire")
+
+    @property
+    def wire(self) -> int:
+        rc = load().inccl_comm_wire(self.handle)
+        if rc < 0:
+            check(rc, "inccl_comm_wire")
+        return rc
 
     # -- reference collectives on host int32 arrays (api.c:330-452) --
     def allreduce_write(self, src: np.ndarray, length: int, dst: np.ndarray) -> None:

@@ -60,6 +60,8 @@ extern "C" {
 #define INCCL_KIND_F16 4     /* IEEE binary16 gradient: quantised as the fp32 it widens to exactly;
                                 dequantised as f16_rne((float)s * 2^-k) (+-Inf past 65504).
                                 Pairs: F16->F16, F16->Q32, Q32->F16 */
+#define INCCL_KIND_P16 5     /* packed 16-bit lanes: two per-block scaled fixed-point elements an int32
+                                word (inccl_stream_op_block only).  Pairs: F32->P16, P16->F32 */
 
 const char *inccl_last_error(void);
 const char *inccl_version(void);
@@ -144,6 +146,36 @@ int inccl_reduce_f32_block(const float *const *srcs_dev, int R, float *dst_dev, 
  * words.  scale_R: the contributors the exponents are chosen for (0: R). */
 int inccl_stream_op_block(int in_kind, int out_kind, const void *const *srcs_dev, int R, void *dst_dev, size_t n,
                           const uint32_t *words_dev, size_t elem_base, int scale_R, void *stream);
+/* ---- packed 16-bit lanes (INCCL_KIND_P16): per-block scaling at 2 bytes an element ----
+ * Blocks and words are INCCL_SCALE_BLOCK's.  With a per-block exponent a
+ * 16-bit fixed-point lane keeps 10-13 significant bits of the block's largest
+ * element, two lanes fit an int32 word, and the unchanged wrap-around int32 sum
+ * of such words (inccl_sum_q32, every engine's int32 exchange) adds both lanes
+ * at once:
+ *   k_b   = max(inccl_choose_scale_word(w_b, R_total) - 16, INCCL_SCALE_MIN)   (a zero block: 48)
+ *   L     = 32767 / R_total                       (R_total > 32767: INCCL_ERR_ARG)
+ *   q     = clamp(sat_int32(round_half_even(x * 2^k_b)), -L, L), NaN -> 0; the
+ *           clamp binds only for +-Inf and where k_b was clamped at INCCL_SCALE_MIN
+ *   word j of a bucket = q[2j + 1] * 65536 + q[2j] mod 2^32; n odd: the last
+ *           word's high lane is 0; a bucket is ceil(n / 2) words, block b words
+ *           [128 b, 128 b + 128)
+ *   sum   s = sum of words mod 2^32; lo = sign_extend16(s), hi = (s - lo) >> 16
+ *           (arithmetic): each lane's sum exactly, since it lies in [-32767, 32767]
+ *   y     = (float)lane * 2^-k_b, exact; NaN with bit 31 of w_b set
+ * Every lane of the result is within R_total * 2^-(k_b + 1) + |sum| * 2^-23 of
+ * the exact sum: 16 bits coarser than INCCL_SCALE_BLOCK's 32-bit lanes.  Meant
+ * for 2-16 contributors: past about 16 it is less accurate than rounding the
+ * buckets to bf16 (Numerics).
+ *
+ * inccl_stream_op_block takes the pairs F32 -> P16 (dst_dev: ceil(n / 2) words;
+ * elem_base must be even, else INCCL_ERR_ARG) and P16 -> F32 (n: elements of
+ * dst_dev; srcs_dev point at the word that holds element elem_base, whose low
+ * lane is skipped when elem_base is odd).
+ *
+ * The fused one-pass form of inccl_reduce_f32_block at these semantics, R_total
+ * = R: fp32 in, fp32 out, what the packed exchange of R ranks would give. */
+int inccl_reduce_f32_block16(const float *const *srcs_dev, int R, float *dst_dev, size_t n, uint32_t *words_out_dev,
+                             int flags, void *stream);
 /* Position-weighted linear checksum sum_i (2(base+i)+1)*q[i] mod 2^32 into *out_dev. */
 int inccl_checksum_q32(const int32_t *q_dev, size_t n, uint64_t index_base, uint32_t *out_dev, int zero_first,
                        void *stream);
@@ -261,6 +293,21 @@ int inccl_comm_set_average(struct inccl_communicator *comm, int on);
 #define INCCL_NONFINITE_SATURATE 0
 #define INCCL_NONFINITE_NAN 1
 int inccl_comm_set_nonfinite(struct inccl_communicator *comm, int mode);
+/* What the INCCL_SCALE_BLOCK calls of inccl_allreduce_f32, _f32_pipelined and
+ * inccl_reduce_scatter_f32 exchange.  INCCL_WIRE_Q32 (the default): one int32
+ * per element.  INCCL_WIRE_P16: packed 16-bit lanes (INCCL_KIND_P16 above), one
+ * int32 word per two elements through the same int32 exchange of every engine,
+ * so the exchanged bytes halve.  The routes change where a word cannot be
+ * split: reduce-scatter + all-gather becomes the engine's int32 allreduce
+ * (`chunks` is then ignored), and a reduce-scatter whose shards are odd takes
+ * the allreduce and dequantises its shard.  World 1 runs inccl_reduce_f32_block16.
+ * Fixed and INCCL_SCALE_AUTO calls, 16-bit buckets, prepared ops and the host
+ * pipeline are unaffected.  Set it alike on every rank.  inccl_comm_wire
+ * returns the setting. */
+#define INCCL_WIRE_Q32 0
+#define INCCL_WIRE_P16 1
+int inccl_comm_set_wire(struct inccl_communicator *comm, int wire);
+int inccl_comm_wire(struct inccl_communicator *comm);
 
 /* Per-stage timing of this rank's calls (diagnostics; off by default).  on != 0:
  * every later non-captured allreduce / reduce-scatter records a pair of HIP
