@@ -5,7 +5,6 @@
  * arithmetic runs in the HIP kernels behind inccl_kernels.h or in RCCL.
  * There is no CPU fallback: without a usable GPU the calls fail. */
 #define _GNU_SOURCE
-#include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -107,7 +106,7 @@ int inccl_stream_op(int in_kind, int out_kind, const void *const *srcs_dev, int 
 {
     if (!srcs_dev) return inccl_set_error(INCCL_ERR_ARG, "srcs is NULL");
     if (scale_exp == INCCL_SCALE_BLOCK && !amax_bits_dev) return block_refused("a fixed-exponent stream op");
-    return kerr(inccl_k_stream(in_kind, out_kind, srcs_dev, R, dst_dev, n, scale_exp, amax_bits_dev, scale_R, stream));
+    return kerr(inccl_k_stream(in_kind, out_kind, srcs_dev, R, dst_dev, n, scale_exp, amax_bits_dev, scale_R, 0, stream));
 }
 
 /* ---- per-block auto scaling, stateless (include/inccl_amd.h) ---- */
@@ -357,7 +356,7 @@ int inccl_op_run(struct inccl_op *op)
         return allreduce_any(op->comm, op->in_kind, op->srcs, op->R, op->dst, op->n, op->scale_exp, op->chunks,
                              op->stream);
     return kerr(inccl_k_stream(op->in_kind, op->out_kind, op->srcs, op->R, op->dst, op->n, op->scale_exp, NULL,
-                               op->scale_R, op->stream));
+                               op->scale_R, 0, op->stream));
 }
 
 int inccl_op_destroy(struct inccl_op *op)
@@ -447,29 +446,15 @@ int inccl_checksum_q32(const int32_t *q_dev, size_t n, uint64_t index_base, uint
     return kerr(inccl_k_checksum(q_dev, n, index_base, out_dev, zero_first, stream));
 }
 
-int inccl_choose_scale(float absmax, int R_total)
-{
-    /* host twin of choose_scale() in inccl_kernels.hip */
-    if (!(absmax > 0.0f)) return INCCL_SCALE_MAX;
-    if (isinf(absmax)) return INCCL_SCALE_MIN;
-    double t = (double)absmax * (double)(R_total > 0 ? R_total : 1);
-    int e = 0;
-    double m = frexp(t, &e);
-    int k = (m == 0.5) ? (31 - e) : (30 - e);
-    if (k < INCCL_SCALE_MIN) k = INCCL_SCALE_MIN;
-    if (k > INCCL_SCALE_MAX) k = INCCL_SCALE_MAX;
-    return k;
-}
+/* the auto scale rule: stated once, in inccl_scale_rule.h (host and device) */
+int inccl_choose_scale(float absmax, int R_total) { return inccl_scale_of_float(absmax, R_total); }
 
 /* The host's reading of an absmax word (resolve_scale below: the IPC engines
  * agree the word on the host): the flag bit apart, the rule on the magnitude. */
 int inccl_choose_scale_word(uint32_t absmax_word, int R_total, int *nonfinite)
 {
-    const uint32_t bits = absmax_word & 0x7fffffffu;
-    float amax;
-    memcpy(&amax, &bits, sizeof(amax));
     if (nonfinite) *nonfinite = (int)(absmax_word >> 31);
-    return inccl_choose_scale(amax, R_total);
+    return inccl_scale_of_word(absmax_word, R_total);
 }
 
 void inccl_set_tuning(int grid_cap, int nt_loads) { inccl_k_set_tuning(grid_cap, nt_loads); }
@@ -994,10 +979,10 @@ static int resolve_block_scale(struct inccl_communicator *c, const void *const *
  * takes the absmax of the local buckets (kind F32, BF16 or F16) and its max over
  * the group (with bit 31 set when a rank saw a NaN or +-Inf and the
  * communicator propagates them, inccl_comm_set_nonfinite).  On the IPC engines that max is agreed on the host anyway (the node's
- * shared memory), so the host also picks the exponent (inccl_choose_scale, the
- * host twin of the kernels' choose_scale): sc->k, no device word, no copy
- * back.  Otherwise the max stays on the device (sc->amax) for the kernels to
- * resolve. */
+ * shared memory), so the host also picks the exponent (inccl_choose_scale_word,
+ * the rule of inccl_scale_rule.h on the word's magnitude): sc->k, no device
+ * word, no copy back.  Otherwise the max stays on the device (sc->amax) for
+ * the kernels to resolve (inccl_scale_of_device_word, the same header). */
 static int resolve_scale(struct inccl_communicator *c, int kind, const void *const *srcs, int R, size_t n,
                          int scale_exp, hipStream_t st, struct inccl_scale *sc)
 {
@@ -1056,7 +1041,7 @@ static int quant_sum(int kind, const void *const *srcs, int R, int32_t *q, size_
 {
     const int rc = sc->blk ? kerr(inccl_k_stream_block(kind, sc->p16 ? INCCL_KIND_P16 : INCCL_KIND_Q32, srcs, R, q, n,
                                                        sc->blk, sc->nb, sc->blk_base, sc->R, 0, st))
-                           : kerr(inccl_k_stream(kind, INCCL_KIND_Q32, srcs, R, q, n, sc->k, sc->amax, sc->R, st));
+                           : kerr(inccl_k_stream(kind, INCCL_KIND_Q32, srcs, R, q, n, sc->k, sc->amax, sc->R, 0, st));
     if (rc) return rc;
     const size_t nw = wire_words(sc, n), tw = wire_words(sc, total);
     if (tw > nw) INCCL_HIP(hipMemsetAsync(q + nw, 0, (tw - nw) * sizeof(int32_t), st));
@@ -1083,7 +1068,7 @@ static int stage_dequant(struct inccl_communicator *c, int kind, const int32_t *
     const int si = stage_open(c, st);
     const int rc = sc->blk ? kerr(inccl_k_stream_block(sc->p16 ? INCCL_KIND_P16 : INCCL_KIND_Q32, kind, s1, 1, dst, n,
                                                        sc->blk, sc->nb, sc->blk_base + lo, sc->R, c->out_shift, st))
-                           : kerr(inccl_k_stream_s(INCCL_KIND_Q32, kind, s1, 1, dst, n, sc->k, sc->amax, sc->R,
+                           : kerr(inccl_k_stream(INCCL_KIND_Q32, kind, s1, 1, dst, n, sc->k, sc->amax, sc->R,
                                                    c->out_shift, st));
     if (rc) return rc;
     stage_close(c, si, st, INCCL_STAGE_DEQUANT);
@@ -1147,7 +1132,7 @@ static int allreduce_a2a(struct inccl_communicator *c, const void *const *srcs, 
                                                       : (const void *)(qrecv + (size_t)j * shard);
     const size_t lo = (size_t)me * shard;
     float *gather = in_place ? dst : (float *)c->d_f32;
-    rc = kerr(inccl_k_stream_s(INCCL_KIND_Q32, INCCL_KIND_F32, parts, W, gather + lo, shard, sc->k, sc->amax, sc->R,
+    rc = kerr(inccl_k_stream(INCCL_KIND_Q32, INCCL_KIND_F32, parts, W, gather + lo, shard, sc->k, sc->amax, sc->R,
                                c->out_shift, st));
     if (rc) return rc;
     rc = inccl_tp_all_gather(c, gather + lo, gather, shard, sizeof(float), st);
@@ -1306,7 +1291,7 @@ static int allreduce_body(struct inccl_communicator *c, int kind, const void *co
     if (rc) return rc;
     switch (route) {
         case INCCL_ROUTE_FUSED:   /* one HBM pass: quant + sum + dequant */
-            return kerr(inccl_k_stream_s(kind, kind, srcs, R, dst, n, sc.k, sc.amax, sc.R, c->out_shift, st));
+            return kerr(inccl_k_stream(kind, kind, srcs, R, dst, n, sc.k, sc.amax, sc.R, c->out_shift, st));
         case INCCL_ROUTE_RSAG: return allreduce_rsag(c, kind, srcs, R, dst, n, &sc, chunks, st);
         case INCCL_ROUTE_AR: return allreduce_via_q32(c, kind, srcs, R, dst, n, 0, n, &sc, st);
         case INCCL_ROUTE_A2A: return allreduce_a2a(c, srcs, R, (float *)dst, n, &sc, st);
@@ -1406,7 +1391,7 @@ static int reduce_scatter_body(struct inccl_communicator *c, int kind, const voi
     if (rc) return rc;
     switch (route) {
         case INCCL_ROUTE_FUSED:   /* one HBM pass */
-            return kerr(inccl_k_stream_s(kind, kind, srcs, R, dst, n, sc.k, sc.amax, sc.R, c->out_shift, st));
+            return kerr(inccl_k_stream(kind, kind, srcs, R, dst, n, sc.k, sc.amax, sc.R, c->out_shift, st));
         case INCCL_ROUTE_RS: {    /* quant + local sum -> int32 reduce-scatter -> dequantise the shard */
             rc = inccl_ws_claim(c, st);
             if (rc) return rc;

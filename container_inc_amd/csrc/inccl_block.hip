@@ -6,9 +6,8 @@
 //
 //   w_b   bits of max |x| over block b of every bucket of every rank (NaN
 //         ignored; with the non-finite flag a NaN or +-Inf sets bit 31)
-//   k_b   the auto scale rule on w_b (inccl_scale_rule.h: the integer form of
-//         choose_scale, a dozen integer ops, so that no kernel here runs a
-//         double-precision frexp)
+//   k_b   the auto scale rule on w_b (inccl_scale_of_word of inccl_scale_rule.h,
+//         a dozen integer ops; bit 31 of w_b is ignored for the exponent)
 //   q = sat_i32(rne(x * 2^k_b)),  s = sum q mod 2^32,  y = (float)s * 2^-(k_b + out_shift)
 //
 // Kernels:
@@ -40,32 +39,6 @@
 namespace {
 
 using namespace inccl_dev;
-
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const uint32_t o = (uint32_t)__shfl_xor((int)v, off, 64);
-        v = v > o ? v : o;
-    }
-    return v;
-}
-
-// |x| bits; NaN -> 0 (ignored), or with NF a NaN / +-Inf -> bit 31 | its bits
-// (abs_bits of inccl_kernels.hip)
-template <bool NF>
-__device__ __forceinline__ uint32_t abs_bits(uint32_t b)
-{
-    const uint32_t a = b & 0x7fffffffu;
-    if constexpr (NF) return a >= 0x7f800000u ? 0x80000000u | a : a;
-    else return a > 0x7f800000u ? 0u : a;
-}
-
-template <bool NF>
-__device__ __forceinline__ uint32_t amax_quad(u32x4 x)
-{
-    return max(max(abs_bits<NF>(x.x), abs_bits<NF>(x.y)), max(abs_bits<NF>(x.z), abs_bits<NF>(x.w)));
-}
 
 __device__ __forceinline__ uint32_t fused1(uint32_t acc, float inv) { return store_xform<F32>(acc, inv); }
 
@@ -131,11 +104,7 @@ __global__ __launch_bounds__(BLOCK) void k_stream_block_fused(SrcPtrs src, void*
                 acc.z += quantb<P16>(__uint_as_float(v[r][u].z), bm.scale, L);
                 acc.w += quantb<P16>(__uint_as_float(v[r][u].w), bm.scale, L);
             }
-            u32x4 o;
-            o.x = fused1(acc.x, bm.inv);
-            o.y = fused1(acc.y, bm.inv);
-            o.z = fused1(acc.z, bm.inv);
-            o.w = fused1(acc.w, bm.inv);
+            const u32x4 o = xform_quad<F32>(acc, bm.inv);
             if (full)
                 __builtin_amdgcn_raw_buffer_store_b128(o, orsrc, (int)((threadIdx.x + u * BLOCK) * 16), 0, kAuxSc1);
             else if (i < n4)
@@ -260,18 +229,8 @@ __global__ __launch_bounds__(BLOCK) void k_stream_block(SrcPtrs src, void* __res
         const BlockMul bm = block_mul(word_at(words, (elem_base + (i << 2)) >> 8, nb), scale_R, out_shift);
         u32x4 acc = {0u, 0u, 0u, 0u};
 #pragma unroll
-        for (int r = 0; r < R; ++r) {
-            acc.x += load_xform<IN>(v[r].x, bm.scale);
-            acc.y += load_xform<IN>(v[r].y, bm.scale);
-            acc.z += load_xform<IN>(v[r].z, bm.scale);
-            acc.w += load_xform<IN>(v[r].w, bm.scale);
-        }
-        u32x4 o;
-        o.x = store_xform<OUT>(acc.x, bm.inv);
-        o.y = store_xform<OUT>(acc.y, bm.inv);
-        o.z = store_xform<OUT>(acc.z, bm.inv);
-        o.w = store_xform<OUT>(acc.w, bm.inv);
-        out[i] = o;
+        for (int r = 0; r < R; ++r) accum_quad<IN>(acc, v[r], bm.scale);
+        out[i] = xform_quad<OUT>(acc, bm.inv);
     }
 }
 
@@ -316,12 +275,10 @@ void launch_fused(const SrcPtrs& s, void* dst, int64_t n, uint32_t* words, int s
     if (vec) {
         constexpr int B = Geometry<R>::BLOCK, U = Geometry<R>::U;
         // one workgroup per tile, as the single-scale fused kernel
-        const int64_t tiles = (nb * 64 + (int64_t)B * U - 1) / ((int64_t)B * U);
-        const int grid = (int)(tiles < 0x7fffffff ? tiles : 0x7fffffff);
-        hipLaunchKernelGGL((k_stream_block_fused<R, NF, P16, B, U>), dim3(grid), dim3(B), 0, st, s, dst, n, words, scale_R,
-                           out_shift);
+        hipLaunchKernelGGL((k_stream_block_fused<R, NF, P16, B, U>), dim3(grid_capped(nb * 64, B * U, kNoCap)), dim3(B), 0,
+                           st, s, dst, n, words, scale_R, out_shift);
     } else {
-        hipLaunchKernelGGL((k_block_fused_elem<R, NF, P16>), dim3(grid_of(nb, kBlkWaves)), dim3(kBlock), 0, st, s, dst, n,
+        hipLaunchKernelGGL((k_block_fused_elem<R, NF, P16>), dim3(grid_of(nb, kBlkWaves, 8)), dim3(kBlock), 0, st, s, dst, n,
                            words, scale_R, out_shift);
     }
 }
@@ -329,7 +286,7 @@ void launch_fused(const SrcPtrs& s, void* dst, int64_t n, uint32_t* words, int s
 template <int R, bool NF>
 void launch_absmax(const SrcPtrs& s, int64_t n, uint32_t* words, bool vec, hipStream_t st)
 {
-    hipLaunchKernelGGL((k_block_absmax<R, NF>), dim3(grid_of((n + 255) >> 8, kBlkWaves)), dim3(kBlock), 0, st, s, n,
+    hipLaunchKernelGGL((k_block_absmax<R, NF>), dim3(grid_of((n + 255) >> 8, kBlkWaves, 8)), dim3(kBlock), 0, st, s, n,
                        words, vec ? 1 : 0);
 }
 
@@ -342,12 +299,12 @@ void launch_stream(const SrcPtrs& s, void* dst, int64_t n, const uint32_t* words
     if (vec && (elem_base & 3) == 0) {
         const int64_t n4 = n >> 2;
         if (n4 > 0)
-            hipLaunchKernelGGL((k_stream_block<IN, OUT, R, B>), dim3(grid_of(n4, B)), dim3(B), 0, st, s, dst, n4, words,
+            hipLaunchKernelGGL((k_stream_block<IN, OUT, R, B>), dim3(grid_of(n4, B, 8)), dim3(B), 0, st, s, dst, n4, words,
                                nb, elem_base, scale_R, out_shift);
         done = n4 << 2;
     }
     if (done < n)
-        hipLaunchKernelGGL((k_stream_block_elem<IN, OUT, R>), dim3(grid_of(n - done, kBlock)), dim3(kBlock), 0, st, s,
+        hipLaunchKernelGGL((k_stream_block_elem<IN, OUT, R>), dim3(grid_of(n - done, kBlock, 8)), dim3(kBlock), 0, st, s,
                            dst, done, n, words, nb, elem_base, scale_R, out_shift);
 }
 
@@ -429,7 +386,7 @@ int inccl_k_words_max(const uint32_t* rows_dev, int W, size_t nb, uint32_t* out_
 {
     if (W < 1 || ((rows_dev == nullptr || out_dev == nullptr) && nb > 0)) return INCCL_ERR_ARG;
     if (nb == 0) return 0;
-    hipLaunchKernelGGL(k_words_max, dim3(grid_of((int64_t)nb, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, rows_dev,
+    hipLaunchKernelGGL(k_words_max, dim3(grid_of((int64_t)nb, kBlock, 8)), dim3(kBlock), 0, (hipStream_t)stream, rows_dev,
                        W, (int64_t)nb, out_dev);
     return (int)hipGetLastError();
 }

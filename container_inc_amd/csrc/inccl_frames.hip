@@ -41,6 +41,7 @@
 #include <mutex>
 
 #include "inccl_frames.h"
+#include "inccl_launch.h"
 
 namespace {
 
@@ -1865,20 +1866,6 @@ int ensure_tables()
     return 0;
 }
 
-int num_cus()
-{
-    static int cus = 0;
-    if (cus == 0) {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) == hipSuccess &&
-            hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
-            cus = v;
-        else
-            cus = 256;
-    }
-    return cus;
-}
-
 // classify (a lane per frame), then sum (a wave per pair of frames, short-lived blocks)
 int launch_apply(const ApplyArgs& a, hipStream_t st)
 {
@@ -1904,8 +1891,7 @@ int launch_egress_t(const EgressArgs& a, hipStream_t st)
         return n;
     }();
     const int64_t chunks = ((int64_t)a.count + egress_chunk(a.fan) - 1) / egress_chunk(a.fan);
-    const int64_t need = (chunks + kEgressWaves - 1) / kEgressWaves, cap = (int64_t)num_cus() * per_cu;
-    hipLaunchKernelGGL((k_egress<kFan, kOut16, kNR>), dim3((unsigned)(need < cap ? (need < 1 ? 1 : need) : cap)),
+    hipLaunchKernelGGL((k_egress<kFan, kOut16, kNR>), dim3(inccl_dev::grid_of(chunks, kEgressWaves, per_cu)),
                        dim3(kWave * kEgressWaves), 0, st, a);
     return (int)hipGetLastError();
 }
@@ -1994,8 +1980,7 @@ int launch_nr_ingress(const InccSwitchState* s, const uint8_t* frames, size_t st
     const bool wide = ((uintptr_t)frames & 15) == 0 && (stride & 15) == 0;
     // whole groups of kNrShards waves (every region gets the same number of waves)
     constexpr int64_t group = kNrShards / kNrSumWaves;
-    const int64_t need = (n + kNrSumWaves - 1) / kNrSumWaves, cap = (int64_t)num_cus() * 8;
-    const int64_t blocks = ((need < cap ? need : cap) + group - 1) / group * group;
+    const int64_t blocks = (inccl_dev::grid_of(n, kNrSumWaves, 8) + group - 1) / group * group;
     if (wide)
         hipLaunchKernelGGL(k_nr_sum<true>, dim3((unsigned)blocks), dim3(kWave * kNrSumWaves), 0, st, *s, frames,
                            (int64_t)stride, n);
@@ -2035,11 +2020,10 @@ int inccl_k_icrc(const uint8_t* frames, size_t stride, size_t count, uint32_t* o
     hipStream_t st = (hipStream_t)stream;
     // 8-wave blocks, four per CU (20.7 KiB of tables each); the output buffer's
     // byte size is a 32-bit field, so very large counts go in pieces
-    const int64_t piece = (int64_t)1 << 28, cap = (int64_t)num_cus() * 4;
+    const int64_t piece = (int64_t)1 << 28;
     for (int64_t f = 0; f < (int64_t)count; f += piece) {
         const int64_t n = (int64_t)count - f < piece ? (int64_t)count - f : piece;
-        const int64_t need = ((n + 1) / 2 + 7) / 8;
-        hipLaunchKernelGGL(k_icrc<8>, dim3((unsigned)(need < cap ? need : cap)), dim3(kWave * 8), 0, st,
+        hipLaunchKernelGGL(k_icrc<8>, dim3(inccl_dev::grid_of((n + 1) / 2, 8, 4)), dim3(kWave * 8), 0, st,
                            frames + f * (int64_t)stride, (int64_t)stride, n, out + f);
     }
     return (int)hipGetLastError();

@@ -1,5 +1,6 @@
 /* inccl_kernels.h -- the thin C-ABI shim between the C host code and the HIP
- * kernels in inccl_kernels.hip.  Internal to libinccl_amd.so. */
+ * kernels of the seven .hip files (inccl_kernels, _block, _pack, _peer, _ll,
+ * _mesh; inccl_frames.hip has inccl_frames.h).  Internal to libinccl_amd.so. */
 #ifndef INCCL_KERNELS_H
 #define INCCL_KERNELS_H
 
@@ -12,12 +13,10 @@
 extern "C" {
 #endif
 
-/* out[i] = OUT(sum_r IN(srcs[r][i])), kinds INCCL_KIND_*.  Returns 0 or a hipError_t / INCCL_ERR_ARG. */
+/* out[i] = OUT(sum_r IN(srcs[r][i])), kinds INCCL_KIND_*; the dequantise is scaled by 2^-out_shift
+ * (inccl_comm_set_average; 0: the plain sum).  Returns 0 or a hipError_t / INCCL_ERR_ARG. */
 int inccl_k_stream(int in_kind, int out_kind, const void *const *srcs, int R, void *dst, size_t n, int scale_exp,
-                   const uint32_t *amax_bits_dev, int scale_R, void *stream);
-/* the same with the dequantise scaled by 2^-out_shift (inccl_comm_set_average) */
-int inccl_k_stream_s(int in_kind, int out_kind, const void *const *srcs, int R, void *dst, size_t n, int scale_exp,
-                     const uint32_t *amax_bits_dev, int scale_R, int out_shift, void *stream);
+                   const uint32_t *amax_bits_dev, int scale_R, int out_shift, void *stream);
 /* absmax word of R buckets of kind F32 / BF16 / F16 (include/inccl_amd.h inccl_absmax_*) */
 int inccl_k_absmax(int kind, const void *const *srcs, int R, size_t n, uint32_t *amax_bits_dev, int zero_first,
                    void *stream);

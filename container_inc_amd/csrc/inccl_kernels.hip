@@ -32,7 +32,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "inccl_kernels.h"
+#include "inccl_launch.h"
 #include "inccl_stream.h"
 
 namespace {
@@ -85,37 +85,8 @@ __global__ __launch_bounds__(kBlock) void k_stream16_scalar(SrcPtrs src, void* _
     }
 }
 
-// ---- horizontal reductions: wave64 shuffle -> LDS -> one atomic per block ----
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const uint32_t o = (uint32_t)__shfl_xor((int)v, off, 64);
-        v = v > o ? v : o;
-    }
-    return v;
-}
-
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += (uint32_t)__shfl_xor((int)v, off, 64);
-    return v;
-}
-
-// |x| bits of a float; NaN -> 0 (ignored, as orc_absmax_f32).  Non-negative
-// IEEE floats order like their bit patterns, so max over bits == max over values.
-// NF (INCCL_ABSMAX_FLAG_NONFINITE): a NaN or +-Inf instead sets bit 31, which
-// no |x| has, so the max over every element -- and over the ranks -- carries it
-// (deq_scale then makes every result NaN).
-template <bool NF = false>
-__device__ __forceinline__ uint32_t abs_bits(uint32_t b)
-{
-    const uint32_t a = b & 0x7fffffffu;
-    if constexpr (NF) return a >= 0x7f800000u ? 0x80000000u | a : a;
-    else return a > 0x7f800000u ? 0u : a;
-}
-
+// ---- horizontal reductions: wave64 shuffle (wave_max_u32 / wave_sum_u32 of
+// inccl_stream.h, as abs_bits and the fp32 amax_quad) -> LDS -> one atomic per block ----
 // absmax over 2-byte buckets (E: BF16 or F16), as the fp32 bits of the widened values
 template <bool NF>
 __device__ __forceinline__ uint32_t abs_bits_bf16(uint32_t h) { return abs_bits<NF>(h << 16); }
@@ -130,7 +101,7 @@ __device__ __forceinline__ uint32_t abs_bits16(uint32_t h)
 
 // element kind of k_absmax: F32, BF16 or F16
 template <int E, bool NF>
-__device__ __forceinline__ uint32_t amax_quad(u32x4 x)
+__device__ __forceinline__ uint32_t amax_quad_of(u32x4 x)
 {
     if constexpr (E != F32)
         return max(max(max(abs_bits16<E, NF>(x.x & 0xffffu), abs_bits16<E, NF>(x.x >> 16)),
@@ -138,7 +109,7 @@ __device__ __forceinline__ uint32_t amax_quad(u32x4 x)
                    max(max(abs_bits16<E, NF>(x.z & 0xffffu), abs_bits16<E, NF>(x.z >> 16)),
                        max(abs_bits16<E, NF>(x.w & 0xffffu), abs_bits16<E, NF>(x.w >> 16))));
     else
-        return max(max(abs_bits<NF>(x.x), abs_bits<NF>(x.y)), max(abs_bits<NF>(x.z), abs_bits<NF>(x.w)));
+        return amax_quad<NF>(x);
 }
 
 // max |x| over R buckets of fp32 (E = F32), bf16 or fp16 elements.
@@ -171,7 +142,7 @@ __global__ __launch_bounds__(kAmBlock) void k_absmax(SrcPtrs src, int64_t n, uin
         for (int r = 0; r < R; ++r)
 #pragma unroll
             for (int u = 0; u < kAmU; ++u) {
-                const uint32_t a = amax_quad<E, NF>(v[r][u]);
+                const uint32_t a = amax_quad_of<E, NF>(v[r][u]);
                 m = m > a ? m : a;
             }
     }
@@ -226,41 +197,26 @@ __global__ __launch_bounds__(kBlock) void k_checksum(const uint32_t* __restrict_
 // ---------------------------------------------------------------------------
 // host-side dispatch
 // ---------------------------------------------------------------------------
-int g_num_cus = 0;
 int g_grid_cap = 0;   // 0 -> default; settable for tuning sweeps
 bool g_nt_loads = true;
 
-int num_cus()
+// One workgroup per tile by default (measured on MI355X, 2 x 256 MiB fused:
+// one-shot 6.51 TB/s vs 6.23 TB/s for a 16-per-CU grid-stride cap).
+int stream_grid(int64_t groups, int per_tile)
 {
-    if (g_num_cus == 0) {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) == hipSuccess &&
-            hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
-            g_num_cus = v;
-        else
-            g_num_cus = 256;
-    }
-    return g_num_cus;
+    return grid_capped(groups, per_tile, g_grid_cap > 0 ? g_grid_cap : kNoCap);
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 template <int IN, int OUT, int R>
-int launch_stream_R(const SrcPtrs& s, void* dst, int64_t n, const Scale& sc, hipStream_t st)
+int launch_stream_R(const SrcPtrs& s, bool vec, void* dst, int64_t n, const Scale& sc, hipStream_t st)
 {
-    bool vec = aligned16(dst);
-    for (int r = 0; r < R; ++r) vec = vec && aligned16(s.p[r]);
     int64_t done = 0;
     if (vec) {
         const int64_t n4 = n >> 2;
         if (n4 > 0) {
             constexpr int U = Geometry<R>::U;
             constexpr int B = Geometry<R>::BLOCK;
-            const int64_t tiles = (n4 + (int64_t)B * U - 1) / ((int64_t)B * U);
-            // One workgroup per tile by default (measured on MI355X, 2 x 256 MiB
-            // fused: one-shot 6.51 TB/s vs 6.23 TB/s for a 16-per-CU grid-stride cap).
-            const int64_t cap = g_grid_cap > 0 ? g_grid_cap : (int64_t)0x7fffffff;
-            const int grid = (int)(tiles < cap ? tiles : cap);
+            const int grid = stream_grid(n4, B * U);
             if (g_nt_loads)
                 hipLaunchKernelGGL((k_stream_vec<IN, OUT, R, true, B, U>), dim3(grid), dim3(B), 0, st, s, dst, n4, sc);
             else
@@ -269,11 +225,8 @@ int launch_stream_R(const SrcPtrs& s, void* dst, int64_t n, const Scale& sc, hip
         done = n4 << 2;
     }
     if (done < n) {
-        const int64_t rem = n - done;
-        int64_t blocks = (rem + kBlock - 1) / kBlock;
-        const int64_t cap = (int64_t)num_cus() * 8;
-        const int grid = (int)(blocks < cap ? blocks : cap);
-        hipLaunchKernelGGL((k_stream_scalar<IN, OUT, R>), dim3(grid), dim3(kBlock), 0, st, s, dst, done, n, sc);
+        hipLaunchKernelGGL((k_stream_scalar<IN, OUT, R>), dim3(grid_of(n - done, kBlock, 8)), dim3(kBlock), 0, st, s, dst,
+                           done, n, sc);
     }
     return (int)hipGetLastError();
 }
@@ -283,21 +236,12 @@ int launch_stream(const void* const* srcs, int R, void* dst, int64_t n, const Sc
 {
     if (R < 1 || R > kMaxR) return INCCL_ERR_ARG;
     if (n <= 0) return 0;
-    SrcPtrs s = {};
-    for (int r = 0; r < R; ++r) {
-        if (srcs[r] == nullptr) return INCCL_ERR_ARG;
-        s.p[r] = srcs[r];
-    }
-    switch (R) {
-    case 1: return launch_stream_R<IN, OUT, 1>(s, dst, n, sc, st);
-    case 2: return launch_stream_R<IN, OUT, 2>(s, dst, n, sc, st);
-    case 3: return launch_stream_R<IN, OUT, 3>(s, dst, n, sc, st);
-    case 4: return launch_stream_R<IN, OUT, 4>(s, dst, n, sc, st);
-    case 5: return launch_stream_R<IN, OUT, 5>(s, dst, n, sc, st);
-    case 6: return launch_stream_R<IN, OUT, 6>(s, dst, n, sc, st);
-    case 7: return launch_stream_R<IN, OUT, 7>(s, dst, n, sc, st);
-    default: return launch_stream_R<IN, OUT, 8>(s, dst, n, sc, st);
-    }
+    SrcPtrs s;
+    bool vec = aligned16(dst);
+    if (fill_srcs(srcs, R, &s, &vec)) return INCCL_ERR_ARG;
+#define INCCL_CALL(RR) return launch_stream_R<IN, OUT, RR>(s, vec, dst, n, sc, st)
+    INCCL_R_SWITCH(R, INCCL_CALL)
+#undef INCCL_CALL
 }
 
 // bf16 geometry per R, from tools/tune/tune_bf16.hip on MI355X (256 MiB bf16
@@ -313,28 +257,20 @@ struct B16Geometry {
 };
 
 template <int IN, int OUT, int R>
-int launch_stream16_R(const SrcPtrs& s, void* dst, int64_t n, const Scale& sc, hipStream_t st)
+int launch_stream16_R(const SrcPtrs& s, bool vec, void* dst, int64_t n, const Scale& sc, hipStream_t st)
 {
-    bool vec = aligned16(dst);
-    for (int r = 0; r < R; ++r) vec = vec && aligned16(s.p[r]);
     int64_t done = 0;
     if (vec) {
         const int64_t n8 = n >> 3;
         if (n8 > 0) {
             constexpr int B = B16Geometry<R>::BLOCK, U = B16Geometry<R>::U;
-            const int64_t tiles = (n8 + (int64_t)B * U - 1) / ((int64_t)B * U);
-            const int64_t cap = g_grid_cap > 0 ? g_grid_cap : (int64_t)0x7fffffff;
-            const int grid = (int)(tiles < cap ? tiles : cap);
-            hipLaunchKernelGGL((k_stream16<IN, OUT, R, B, U>), dim3(grid), dim3(B), 0, st, s, dst, n8, sc);
+            hipLaunchKernelGGL((k_stream16<IN, OUT, R, B, U>), dim3(stream_grid(n8, B * U)), dim3(B), 0, st, s, dst, n8, sc);
         }
         done = n8 << 3;
     }
-    if (done < n) {
-        const int64_t blocks = (n - done + kBlock - 1) / kBlock;
-        const int64_t cap = (int64_t)num_cus() * 8;
-        const int grid = (int)(blocks < cap ? blocks : cap);
-        hipLaunchKernelGGL((k_stream16_scalar<IN, OUT, R>), dim3(grid), dim3(kBlock), 0, st, s, dst, done, n, sc);
-    }
+    if (done < n)
+        hipLaunchKernelGGL((k_stream16_scalar<IN, OUT, R>), dim3(grid_of(n - done, kBlock, 8)), dim3(kBlock), 0, st, s, dst,
+                           done, n, sc);
     return (int)hipGetLastError();
 }
 
@@ -343,21 +279,12 @@ int launch_stream16(const void* const* srcs, int R, void* dst, int64_t n, const 
 {
     if (R < 1 || R > kMaxR) return INCCL_ERR_ARG;
     if (n <= 0) return 0;
-    SrcPtrs s = {};
-    for (int r = 0; r < R; ++r) {
-        if (srcs[r] == nullptr) return INCCL_ERR_ARG;
-        s.p[r] = srcs[r];
-    }
-    switch (R) {
-    case 1: return launch_stream16_R<IN, OUT, 1>(s, dst, n, sc, st);
-    case 2: return launch_stream16_R<IN, OUT, 2>(s, dst, n, sc, st);
-    case 3: return launch_stream16_R<IN, OUT, 3>(s, dst, n, sc, st);
-    case 4: return launch_stream16_R<IN, OUT, 4>(s, dst, n, sc, st);
-    case 5: return launch_stream16_R<IN, OUT, 5>(s, dst, n, sc, st);
-    case 6: return launch_stream16_R<IN, OUT, 6>(s, dst, n, sc, st);
-    case 7: return launch_stream16_R<IN, OUT, 7>(s, dst, n, sc, st);
-    default: return launch_stream16_R<IN, OUT, 8>(s, dst, n, sc, st);
-    }
+    SrcPtrs s;
+    bool vec = aligned16(dst);
+    if (fill_srcs(srcs, R, &s, &vec)) return INCCL_ERR_ARG;
+#define INCCL_CALL(RR) return launch_stream16_R<IN, OUT, RR>(s, vec, dst, n, sc, st)
+    INCCL_R_SWITCH(R, INCCL_CALL)
+#undef INCCL_CALL
 }
 
 int dispatch(int in_kind, int out_kind, const void* const* srcs, int R, void* dst, int64_t n, const Scale& sc,
@@ -388,14 +315,9 @@ template <int E>
 int launch_absmax(const void* const* srcs, int R, size_t n, uint32_t* amax_bits_dev, int zero_first, hipStream_t st)
 {
     constexpr bool B16 = E != F32;
-    if (R < 1 || R > kMaxR || amax_bits_dev == nullptr) return INCCL_ERR_ARG;
-    SrcPtrs s = {};
-    int vec = 1;
-    for (int r = 0; r < R; ++r) {
-        if (srcs[r] == nullptr) return INCCL_ERR_ARG;
-        s.p[r] = srcs[r];
-        vec = vec && aligned16(srcs[r]);
-    }
+    SrcPtrs s;
+    bool vec = true;
+    if (amax_bits_dev == nullptr || fill_srcs(srcs, R, &s, &vec)) return INCCL_ERR_ARG;
     if (zero_first & ~(1 | INCCL_ABSMAX_FLAG_NONFINITE)) return INCCL_ERR_ARG;
     if (zero_first & 1) {
         hipError_t e = hipMemsetAsync(amax_bits_dev, 0, sizeof(uint32_t), st);
@@ -403,22 +325,13 @@ int launch_absmax(const void* const* srcs, int R, size_t n, uint32_t* amax_bits_
     }
     const bool nf = (zero_first & INCCL_ABSMAX_FLAG_NONFINITE) != 0;
     if (n == 0) return 0;
-    const int64_t tiles = ((int64_t)(n / (B16 ? 8 : 4)) + (int64_t)kAmBlock * kAmU - 1) / ((int64_t)kAmBlock * kAmU);
-    const int64_t cap = (int64_t)num_cus() * 2;
-    const int grid = (int)(tiles < 1 ? 1 : (tiles < cap ? tiles : cap));
-    switch (R) {
-#define INCCL_AM(RR)                                                                                             \
-    case RR:                                                                                                     \
-        if (nf)                                                                                                  \
-            hipLaunchKernelGGL((k_absmax<RR, E, true>), dim3(grid), dim3(kAmBlock), 0, st, s, (int64_t)n,         \
-                               amax_bits_dev, vec);                                                              \
-        else                                                                                                     \
-            hipLaunchKernelGGL((k_absmax<RR, E, false>), dim3(grid), dim3(kAmBlock), 0, st, s, (int64_t)n,        \
-                               amax_bits_dev, vec);                                                              \
-        break;
-        INCCL_AM(1) INCCL_AM(2) INCCL_AM(3) INCCL_AM(4) INCCL_AM(5) INCCL_AM(6) INCCL_AM(7) INCCL_AM(8)
-#undef INCCL_AM
-    }
+    const int grid = grid_of((int64_t)(n / (B16 ? 8 : 4)), kAmBlock * kAmU, 2);
+    const dim3 g(grid), b(kAmBlock);
+#define INCCL_CALL(RR)                                                                                     \
+    if (nf) hipLaunchKernelGGL((k_absmax<RR, E, true>), g, b, 0, st, s, (int64_t)n, amax_bits_dev, vec);   \
+    else hipLaunchKernelGGL((k_absmax<RR, E, false>), g, b, 0, st, s, (int64_t)n, amax_bits_dev, vec)
+    INCCL_R_SWITCH(R, INCCL_CALL)
+#undef INCCL_CALL
     return (int)hipGetLastError();
 }
 
@@ -426,20 +339,14 @@ int launch_absmax(const void* const* srcs, int R, size_t n, uint32_t* amax_bits_
 
 extern "C" {
 
-int inccl_k_stream_s(int in_kind, int out_kind, const void* const* srcs, int R, void* dst, size_t n, int scale_exp,
-                     const uint32_t* amax_bits_dev, int scale_R, int out_shift, void* stream)
+int inccl_k_stream(int in_kind, int out_kind, const void* const* srcs, int R, void* dst, size_t n, int scale_exp,
+                   const uint32_t* amax_bits_dev, int scale_R, int out_shift, void* stream)
 {
     if (amax_bits_dev == nullptr && !scale_ok(scale_exp)) return INCCL_ERR_ARG;
     if (dst == nullptr && n > 0) return INCCL_ERR_ARG;
     if (out_shift < 0 || out_shift > 8) return INCCL_ERR_ARG;
     Scale sc{scale_exp, amax_bits_dev, scale_R > 0 ? scale_R : R, out_shift};
     return dispatch(in_kind, out_kind, srcs, R, dst, (int64_t)n, sc, (hipStream_t)stream);
-}
-
-int inccl_k_stream(int in_kind, int out_kind, const void* const* srcs, int R, void* dst, size_t n, int scale_exp,
-                   const uint32_t* amax_bits_dev, int scale_R, void* stream)
-{
-    return inccl_k_stream_s(in_kind, out_kind, srcs, R, dst, n, scale_exp, amax_bits_dev, scale_R, 0, stream);
 }
 
 int inccl_k_absmax(int kind, const void* const* srcs, int R, size_t n, uint32_t* amax_bits_dev, int zero_first,
@@ -463,11 +370,8 @@ int inccl_k_checksum(const int32_t* q, size_t n, uint64_t index_base, uint32_t* 
         if (e != hipSuccess) return (int)e;
     }
     if (n == 0) return 0;
-    const int64_t blocks = ((int64_t)(n >> 2) + kBlock - 1) / kBlock;
-    const int64_t cap = (int64_t)num_cus() * 8;
-    const int grid = (int)(blocks < 1 ? 1 : (blocks < cap ? blocks : cap));
-    hipLaunchKernelGGL(k_checksum, dim3(grid), dim3(kBlock), 0, st, reinterpret_cast<const uint32_t*>(q),
-                       (int64_t)n, index_base, out_dev);
+    hipLaunchKernelGGL(k_checksum, dim3(grid_of((int64_t)(n >> 2), kBlock, 8)), dim3(kBlock), 0, st,
+                       reinterpret_cast<const uint32_t*>(q), (int64_t)n, index_base, out_dev);
     return (int)hipGetLastError();
 }
 

@@ -33,7 +33,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 
-#include "inccl_kernels.h"
+#include "inccl_launch.h"
 #include "inccl_stream.h"
 
 namespace {
@@ -107,13 +107,7 @@ __global__ __launch_bounds__(kLLBlock) void k_ll_oneshot(LLArgs a, int vec_src, 
         u32x4 acc = {0u, 0u, 0u, 0u};
         if (vec_src && 4 * q + 4 <= a.n) {
 #pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const u32x4 x = reinterpret_cast<const u32x4*>(a.src.p[r])[q];
-                acc.x += quant1(__uint_as_float(x.x), scale);
-                acc.y += quant1(__uint_as_float(x.y), scale);
-                acc.z += quant1(__uint_as_float(x.z), scale);
-                acc.w += quant1(__uint_as_float(x.w), scale);
-            }
+            for (int r = 0; r < R; ++r) accum_quad<F32>(acc, reinterpret_cast<const u32x4*>(a.src.p[r])[q], scale);
         } else {
             uint32_t s[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
@@ -196,17 +190,8 @@ __global__ __launch_bounds__(kLLBlock) void k_ll_oneshot(LLArgs a, int vec_src, 
             u32x4 acc = {0u, 0u, 0u, 0u};
 #pragma unroll
             for (int j = 0; j < kMaxR; ++j)
-                if (j < a.W) {
-                    acc.x += x[u][j].x;
-                    acc.y += x[u][j].y;
-                    acc.z += x[u][j].z;
-                    acc.w += x[u][j].w;
-                }
-            u32x4 o;
-            o.x = __float_as_uint((float)(int32_t)acc.x * inv);
-            o.y = __float_as_uint((float)(int32_t)acc.y * inv);
-            o.z = __float_as_uint((float)(int32_t)acc.z * inv);
-            o.w = __float_as_uint((float)(int32_t)acc.w * inv);
+                if (j < a.W) accum_quad<Q32>(acc, x[u][j], 0.0f);
+            const u32x4 o = xform_quad<F32>(acc, inv);
             if (vec_dst && 4 * qo + 4 <= out_n) {
                 // write-through (sc1): nothing of dst stays dirty in this XCD's L2
                 __builtin_amdgcn_raw_buffer_store_b128(o, dst_rs, (int)(qo * 16), 0, 16);
@@ -243,8 +228,6 @@ hipError_t launch_R(const LLArgs& a, int grid, int vs, int vd, hipStream_t st)
     return hipGetLastError();
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 }  // namespace
 
 // Workgroups per call: one per 256 quads up to a cap ($INCCL_LL_GRID_CAP, which
@@ -260,10 +243,7 @@ extern "C" int inccl_k_ll_grid(size_t n)
         const int v = e ? atoi(e) : 0;
         cap = (v >= 1 && v <= INCCL_LL_MAX_BLOCKS) ? v : kLLDefaultCap;
     }
-    const int64_t nq = ((int64_t)n + 3) >> 2;
-    int64_t g = (nq + kLLBlock - 1) / kLLBlock;
-    if (g > cap) g = cap;
-    return g < 1 ? 1 : (int)g;
+    return grid_capped(((int64_t)n + 3) >> 2, kLLBlock, cap);
 }
 
 extern "C" int inccl_k_ll_oneshot(const struct inccl_ll_launch* l, void* stream)
@@ -299,15 +279,8 @@ extern "C" int inccl_k_ll_oneshot(const struct inccl_ll_launch* l, void* stream)
     const int grid = inccl_k_ll_grid(l->n);
     hipStream_t st = (hipStream_t)stream;
     hipError_t e;
-    switch (l->R) {
-        case 1: e = launch_R<1>(a, grid, vs, vd, st); break;
-        case 2: e = launch_R<2>(a, grid, vs, vd, st); break;
-        case 3: e = launch_R<3>(a, grid, vs, vd, st); break;
-        case 4: e = launch_R<4>(a, grid, vs, vd, st); break;
-        case 5: e = launch_R<5>(a, grid, vs, vd, st); break;
-        case 6: e = launch_R<6>(a, grid, vs, vd, st); break;
-        case 7: e = launch_R<7>(a, grid, vs, vd, st); break;
-        default: e = launch_R<8>(a, grid, vs, vd, st); break;
-    }
+#define INCCL_CALL(RR) e = launch_R<RR>(a, grid, vs, vd, st)
+    INCCL_R_SWITCH(l->R, INCCL_CALL)
+#undef INCCL_CALL
     return e == hipSuccess ? 0 : (int)e;
 }

@@ -58,7 +58,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "inccl_kernels.h"
+#include "inccl_launch.h"
 #include "inccl_stream.h"
 
 namespace {
@@ -269,12 +269,7 @@ __device__ bool do_push(const MeshArgs& a, int c, int j, uint32_t epoch, float s
             for (int u = 0; u < kMeshU; ++u) {
                 acc[u] = u32x4{0u, 0u, 0u, 0u};
 #pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    acc[u].x += quant1(__uint_as_float(x[u][r].x), scale);
-                    acc[u].y += quant1(__uint_as_float(x[u][r].y), scale);
-                    acc[u].z += quant1(__uint_as_float(x[u][r].z), scale);
-                    acc[u].w += quant1(__uint_as_float(x[u][r].w), scale);
-                }
+                for (int r = 0; r < R; ++r) accum_quad<F32>(acc[u], x[u][r], scale);
             }
         } else {   // ragged end of the bucket / unaligned sources: element-granular, zero past n
 #pragma unroll
@@ -366,12 +361,7 @@ __device__ bool do_reduce(const MeshArgs& a, int c, uint32_t epoch, float inv)
             if (q >= nq) break;
             u32x4 acc = {0u, 0u, 0u, 0u};
 #pragma unroll
-            for (int j = 0; j < kMaxR; ++j) {
-                acc.x += x[u][j].x;
-                acc.y += x[u][j].y;
-                acc.z += x[u][j].z;
-                acc.w += x[u][j].w;
-            }
+            for (int j = 0; j < kMaxR; ++j) accum_quad<Q32>(acc, x[u][j], 0.0f);
             if constexpr (is16(E)) {
                 const u32x2 o = {deq16x2<E>(acc.x, acc.y, inv), deq16x2<E>(acc.z, acc.w, inv)};
                 if (push) {
@@ -382,11 +372,7 @@ __device__ bool do_reduce(const MeshArgs& a, int c, uint32_t epoch, float inv)
                     __builtin_amdgcn_raw_buffer_store_b64(o, res, (int)(q * 8), 0, kAuxSys);
                 }
             } else {
-                u32x4 o;
-                o.x = __float_as_uint((float)(int32_t)acc.x * inv);
-                o.y = __float_as_uint((float)(int32_t)acc.y * inv);
-                o.z = __float_as_uint((float)(int32_t)acc.z * inv);
-                o.w = __float_as_uint((float)(int32_t)acc.w * inv);
+                const u32x4 o = xform_quad<F32>(acc, inv);
                 if (push) {
 #pragma unroll
                     for (int j = 0; j < kMaxR; ++j)
@@ -556,8 +542,6 @@ __global__ __launch_bounds__(kMeshBlock) void k_mesh(MeshArgs a)
     }
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 }  // namespace
 
 extern "C" int inccl_k_mesh(const struct inccl_mesh_launch* l, void* stream)
@@ -610,21 +594,12 @@ extern "C" int inccl_k_mesh(const struct inccl_mesh_launch* l, void* stream)
     a.zero = 0;
     hipStream_t st = (hipStream_t)stream;
     const dim3 g((unsigned)l->grid), b(kMeshBlock);
-#define INCCL_MESH_CASE(RR)                                                  \
-    case RR:                                                                 \
-        if (l->kind16 == F16)                                                \
-            hipLaunchKernelGGL((k_mesh<RR, F16>), g, b, 0, st, a);           \
-        else if (l->kind16 == BF16)                                          \
-            hipLaunchKernelGGL((k_mesh<RR, BF16>), g, b, 0, st, a);          \
-        else                                                                 \
-            hipLaunchKernelGGL((k_mesh<RR, 0>), g, b, 0, st, a);             \
-        break;
-    switch (l->R) {
-        INCCL_MESH_CASE(1) INCCL_MESH_CASE(2) INCCL_MESH_CASE(3) INCCL_MESH_CASE(4) INCCL_MESH_CASE(5)
-        INCCL_MESH_CASE(6) INCCL_MESH_CASE(7)
-        default: INCCL_MESH_CASE(8)
-    }
-#undef INCCL_MESH_CASE
+#define INCCL_CALL(RR)                                                                  \
+    if (l->kind16 == F16) hipLaunchKernelGGL((k_mesh<RR, F16>), g, b, 0, st, a);        \
+    else if (l->kind16 == BF16) hipLaunchKernelGGL((k_mesh<RR, BF16>), g, b, 0, st, a); \
+    else hipLaunchKernelGGL((k_mesh<RR, 0>), g, b, 0, st, a)
+    INCCL_R_SWITCH(l->R, INCCL_CALL)
+#undef INCCL_CALL
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : (int)e;
 }

@@ -170,12 +170,12 @@ void launch_pack(const SrcPtrs& s, void* dst, int64_t n, const uint32_t* words, 
     if (vec && (elem_base & 3) == 0) {
         const int64_t ntiles = n >> 9;   // whole waves of 512 elements
         if (ntiles > 0)
-            hipLaunchKernelGGL((k_pack_block<R, B>), dim3(grid_of(ntiles, B / 64)), dim3(B), 0, st, s, dst, ntiles,
+            hipLaunchKernelGGL((k_pack_block<R, B>), dim3(grid_of(ntiles, B / 64, 8)), dim3(B), 0, st, s, dst, ntiles,
                                words, nb, elem_base, scale_R, L);
         done = ntiles << 8;
     }
     if (done < m)
-        hipLaunchKernelGGL((k_pack_block_elem<R>), dim3(grid_of(m - done, kBlock)), dim3(kBlock), 0, st, s, dst, done,
+        hipLaunchKernelGGL((k_pack_block_elem<R>), dim3(grid_of(m - done, kBlock, 8)), dim3(kBlock), 0, st, s, dst, done,
                            n, words, nb, elem_base, scale_R, L);
 }
 
@@ -188,12 +188,12 @@ void launch_unpack(const SrcPtrs& s, void* dst, int64_t n, const uint32_t* words
     if (vec && (elem_base & 7) == 0) {
         const int64_t n8 = n >> 3;
         if (n8 > 0)
-            hipLaunchKernelGGL((k_unpack_block<R, B>), dim3(grid_of(n8, B)), dim3(B), 0, st, s, dst, n8, words, nb,
+            hipLaunchKernelGGL((k_unpack_block<R, B>), dim3(grid_of(n8, B, 8)), dim3(B), 0, st, s, dst, n8, words, nb,
                                elem_base, scale_R, out_shift);
         done = n8 << 3;
     }
     if (done < n)
-        hipLaunchKernelGGL((k_unpack_block_elem<R>), dim3(grid_of(n - done, kBlock)), dim3(kBlock), 0, st, s, dst,
+        hipLaunchKernelGGL((k_unpack_block_elem<R>), dim3(grid_of(n - done, kBlock, 8)), dim3(kBlock), 0, st, s, dst,
                            done, n, words, nb, elem_base, scale_R, out_shift);
 }
 

@@ -21,7 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "inccl_kernels.h"
+#include "inccl_launch.h"
 #include "inccl_stream.h"
 
 namespace {
@@ -68,19 +68,8 @@ __global__ __launch_bounds__(BLOCK) void k_peer_reduce(SrcPtrs src, float* __res
         if (i < n4) {
             u32x4 acc = v[0];
 #pragma unroll
-            for (int r = 1; r < R; ++r) {
-                acc.x += v[r].x;
-                acc.y += v[r].y;
-                acc.z += v[r].z;
-                acc.w += v[r].w;
-            }
-            u32x4 o = acc;
-            if constexpr (DEQ) {
-                o.x = __float_as_uint((float)(int32_t)acc.x * inv);
-                o.y = __float_as_uint((float)(int32_t)acc.y * inv);
-                o.z = __float_as_uint((float)(int32_t)acc.z * inv);
-                o.w = __float_as_uint((float)(int32_t)acc.w * inv);
-            }
+            for (int r = 1; r < R; ++r) accum_quad<Q32>(acc, v[r], 0.0f);
+            const u32x4 o = xform_quad<DEQ ? F32 : Q32>(acc, inv);
             __builtin_amdgcn_raw_buffer_store_b128(o, rsrc(out + base, tile_bytes), (int)(threadIdx.x * 16u), 0, kAuxWT);
         }
     }
@@ -105,12 +94,7 @@ __global__ __launch_bounds__(BLOCK) void k_peer_reduce16(SrcPtrs src, uint16_t* 
         if (i < n4) {
             u32x4 acc = v[0];
 #pragma unroll
-            for (int r = 1; r < R; ++r) {
-                acc.x += v[r].x;
-                acc.y += v[r].y;
-                acc.z += v[r].z;
-                acc.w += v[r].w;
-            }
+            for (int r = 1; r < R; ++r) accum_quad<Q32>(acc, v[r], 0.0f);
             typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
             const u32x2 o = {deq16x2<K>(acc.x, acc.y, inv), deq16x2<K>(acc.z, acc.w, inv)};
             __builtin_amdgcn_raw_buffer_store_b64(o, rsrc(dst + base * 4, tile_in / 2), (int)(threadIdx.x * 8u), 0,
@@ -177,12 +161,9 @@ template <int R, bool DEQ = true>
 hipError_t launch_reduce_R(const SrcPtrs& s, float* dst, int64_t n4, const Scale& sc, hipStream_t st)
 {
     constexpr int B = Geometry<R>::BLOCK;
-    const int64_t grid = (n4 + B - 1) / B;
-    hipLaunchKernelGGL((k_peer_reduce<R, B, DEQ>), dim3((unsigned)grid), dim3(B), 0, st, s, dst, n4, sc);
+    hipLaunchKernelGGL((k_peer_reduce<R, B, DEQ>), dim3(grid_capped(n4, B, kNoCap)), dim3(B), 0, st, s, dst, n4, sc);
     return hipGetLastError();
 }
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 }  // namespace
 
@@ -196,24 +177,19 @@ extern "C" int inccl_k_peer_reduce(int out_kind, const void* const* peers, int W
         (reinterpret_cast<uintptr_t>(dst) & (half ? 7u : 15u)) != 0)
         return INCCL_ERR_ARG;
     if (n == 0) return 0;
-    SrcPtrs s = {};
-    for (int j = 0; j < W; ++j) {
-        if (peers[j] == nullptr || !aligned16(peers[j])) return INCCL_ERR_ARG;
-        s.p[j] = peers[j];
-    }
+    SrcPtrs s;
+    bool vec = true;
+    if (fill_srcs(peers, W, &s, &vec) || !vec) return INCCL_ERR_ARG;
     Scale sc{scale_exp, amax_bits_dev, scale_R > 0 ? scale_R : W, out_shift};
     const int64_t n4 = (int64_t)(n >> 2);
     hipStream_t st = (hipStream_t)stream;
     float* d = reinterpret_cast<float*>(dst);   // 32-bit words; no float arithmetic without DEQ
     hipError_t e = hipSuccess;
-#define INCCL_BY_W(X) \
-    switch (W) { case 1: X(1) break; case 2: X(2) break; case 3: X(3) break; case 4: X(4) break; \
-                 case 5: X(5) break; case 6: X(6) break; case 7: X(7) break; default: X(8) break; }
-#define INCCL_PR32(WW) e = launch_reduce_R<WW>(s, d, n4, sc, st);
+#define INCCL_PR32(WW) e = launch_reduce_R<WW>(s, d, n4, sc, st)
 #define INCCL_PR16(WW)                                                                                                \
     {                                                                                                                  \
         constexpr int B = Geometry<WW>::BLOCK;                                                                         \
-        const dim3 g((unsigned)((n4 + B - 1) / B));                                                                    \
+        const dim3 g(grid_capped(n4, B, kNoCap));                                                                      \
         uint16_t* d16 = reinterpret_cast<uint16_t*>(dst);                                                              \
         if (out_kind == F16)                                                                                           \
             hipLaunchKernelGGL((k_peer_reduce16<WW, B, F16>), g, dim3(B), 0, st, s, d16, n4, sc);                      \
@@ -221,14 +197,13 @@ extern "C" int inccl_k_peer_reduce(int out_kind, const void* const* peers, int W
             hipLaunchKernelGGL((k_peer_reduce16<WW, B, BF16>), g, dim3(B), 0, st, s, d16, n4, sc);                     \
         e = hipGetLastError();                                                                                         \
     }
-#define INCCL_PRQ(WW) e = launch_reduce_R<WW, false>(s, d, n4, sc, st);
-    if (out_kind == F32) INCCL_BY_W(INCCL_PR32)
-    else if (half) INCCL_BY_W(INCCL_PR16)
-    else INCCL_BY_W(INCCL_PRQ)
+#define INCCL_PRQ(WW) e = launch_reduce_R<WW, false>(s, d, n4, sc, st)
+    if (out_kind == F32) INCCL_R_SWITCH(W, INCCL_PR32)
+    else if (half) INCCL_R_SWITCH(W, INCCL_PR16)
+    else INCCL_R_SWITCH(W, INCCL_PRQ)
 #undef INCCL_PRQ
 #undef INCCL_PR16
 #undef INCCL_PR32
-#undef INCCL_BY_W
     return e == hipSuccess ? 0 : (int)e;
 }
 

@@ -1,8 +1,10 @@
-/* inccl_scale_rule.h -- the INCCL_SCALE_AUTO rule on an absmax WORD, in integer
- * arithmetic.  Pure C, host and device: the per-block kernels (inccl_block.hip)
- * resolve one exponent per 256-element block with it instead of a
- * double-precision frexp, and a stand-alone program walks it against the
- * oracle's rule (tests/c/scale_rule.c).
+/* inccl_scale_rule.h -- the INCCL_SCALE_AUTO rule, stated once for the host and
+ * the device, in integer arithmetic on an absmax WORD.  Pure C: the public
+ * inccl_choose_scale / inccl_choose_scale_word (api.c), the single-scale
+ * kernels' prologue (resolve_k, inccl_stream.h) and the per-block kernels
+ * (block_mul, inccl_block.h: one exponent per 256-element block) all call it,
+ * and a stand-alone program walks it against the oracle's double-precision
+ * rule (tests/c/scale_rule.c).
  *
  * The rule (inccl_choose_scale): amax = 0 or NaN -> INCCL_SCALE_MAX, Inf ->
  * INCCL_SCALE_MIN, else with t = amax * R = m * 2^e, m in [0.5, 1):
@@ -38,6 +40,28 @@ INCCL_HD int inccl_scale_of_word(uint32_t word, int R)
     k = k < INCCL_SCALE_MIN ? INCCL_SCALE_MIN : k;
     k = k > INCCL_SCALE_MAX ? INCCL_SCALE_MAX : k;
     return k;
+}
+
+/* The exponent the single-scale kernels resolve from the device's absmax word
+ * (resolve_k, inccl_stream.h): a word that carries bit 31 gives INCCL_SCALE_MAX,
+ * any other word the rule above.  The float results of a flagged call are NaN
+ * whatever the exponent (deq_scale), and its int32 wire words were always
+ * quantised at INCCL_SCALE_MAX: the flagged word read as a float is negative,
+ * "not greater than 0", which is the oracle's rule on it.  The per-block modes
+ * (block_mul) and the host's inccl_choose_scale_word scale the magnitude
+ * instead. */
+INCCL_HD int inccl_scale_of_device_word(uint32_t word, int R)
+{
+    return (word >> 31) ? INCCL_SCALE_MAX : inccl_scale_of_word(word, R);
+}
+
+/* the rule on a float absmax (inccl_choose_scale): not greater than 0 -- a
+ * negative value carries bit 31 -- or NaN -> INCCL_SCALE_MAX, +Inf -> INCCL_SCALE_MIN */
+INCCL_HD int inccl_scale_of_float(float amax, int R)
+{
+    uint32_t bits;
+    __builtin_memcpy(&bits, &amax, sizeof(bits));
+    return inccl_scale_of_device_word(bits, R);
 }
 
 /* Packed 16-bit lanes (INCCL_KIND_P16): 16 bits less than the 32-bit rule, so

@@ -1,6 +1,8 @@
-// inccl_stream.h -- device code of the generic streaming kernel (HIP, gfx950).
-// Shared by the product (inccl_kernels.hip) and the variant tuner
-// (tools/tune/tune_stream.hip), so the tuner measures exactly this code.
+// inccl_stream.h -- the device code the kernel files share (HIP, gfx950): the
+// scale a kernel resolves, the per-element transforms, the wave reductions and
+// absmax helpers, and the generic streaming kernels.  Shared by the product
+// (the .hip files of this directory) and the variant tuners (tools/tune/*.hip),
+// so the tuners measure exactly this code.
 // See inccl_kernels.hip for the kernel family and the layout.
 #ifndef INCCL_STREAM_H
 #define INCCL_STREAM_H
@@ -9,6 +11,7 @@
 #include <stdint.h>
 
 #include "inccl_amd.h"
+#include "inccl_scale_rule.h"
 
 namespace inccl_dev {
 
@@ -22,7 +25,7 @@ struct SrcPtrs {
 };
 
 // Quantiser scale source: a static exponent, or the absmax word written by
-// k_absmax (auto scaling, spec = orc_choose_scale).
+// k_absmax (auto scaling: inccl_scale_rule.h, whose spec is orc_choose_scale).
 struct Scale {
     int k;
     const uint32_t* amax_bits;  // nullptr -> use k
@@ -32,23 +35,6 @@ struct Scale {
 };
 
 __device__ __forceinline__ float pow2f(int k) { return __uint_as_float((uint32_t)(k + 127) << 23); }
-
-struct Scale;
-__device__ __forceinline__ float deq_scale(const Scale& s, int k);
-
-// Same arithmetic as orc_choose_scale (oracle/inccl_oracle.c).
-__device__ __forceinline__ int choose_scale(float amax, int R)
-{
-    if (!(amax > 0.0f)) return INCCL_SCALE_MAX;
-    if (__builtin_isinf(amax)) return INCCL_SCALE_MIN;
-    double t = (double)amax * (double)R;
-    int e;
-    double m = frexp(t, &e);
-    int k = (m == 0.5) ? (31 - e) : (30 - e);
-    k = k < INCCL_SCALE_MIN ? INCCL_SCALE_MIN : k;
-    k = k > INCCL_SCALE_MAX ? INCCL_SCALE_MAX : k;
-    return k;
-}
 
 // the dequantise multiplier 2^-(k + out_shift); NaN when the auto scale's word
 // carries bit 31 (INCCL_ABSMAX_FLAG_NONFINITE: some input of some rank was NaN
@@ -63,8 +49,7 @@ __device__ __forceinline__ float deq_scale(const Scale& s, int k)
 __device__ __forceinline__ int resolve_k(const Scale& s)
 {
     if (s.amax_bits == nullptr) return s.k;
-    const uint32_t bits = __builtin_nontemporal_load(s.amax_bits);
-    return choose_scale(__uint_as_float(bits), s.scale_R);
+    return inccl_scale_of_device_word(__builtin_nontemporal_load(s.amax_bits), s.scale_R);
 }
 
 // sat_i32(rne(y)) with NaN -> 0: v_rndne_f32 then v_cvt_i32_f32, whose
@@ -99,6 +84,64 @@ __device__ __forceinline__ uint32_t store_xform(uint32_t acc, float inv)
 }
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+// the four lanes of a quad: acc += IN(v), and OUT(acc)
+template <int IN>
+__device__ __forceinline__ void accum_quad(u32x4& acc, u32x4 v, float scale)
+{
+    acc.x += load_xform<IN>(v.x, scale);
+    acc.y += load_xform<IN>(v.y, scale);
+    acc.z += load_xform<IN>(v.z, scale);
+    acc.w += load_xform<IN>(v.w, scale);
+}
+template <int OUT>
+__device__ __forceinline__ u32x4 xform_quad(u32x4 acc, float inv)
+{
+    u32x4 o;
+    o.x = store_xform<OUT>(acc.x, inv);
+    o.y = store_xform<OUT>(acc.y, inv);
+    o.z = store_xform<OUT>(acc.z, inv);
+    o.w = store_xform<OUT>(acc.w, inv);
+    return o;
+}
+
+// ---- horizontal reductions over a wave64: six __shfl_xor steps ----
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const uint32_t o = (uint32_t)__shfl_xor((int)v, off, 64);
+        v = v > o ? v : o;
+    }
+    return v;
+}
+
+__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += (uint32_t)__shfl_xor((int)v, off, 64);
+    return v;
+}
+
+// |x| bits of a float; NaN -> 0 (ignored, as orc_absmax_f32).  Non-negative
+// IEEE floats order like their bit patterns, so max over bits == max over values.
+// NF (INCCL_ABSMAX_FLAG_NONFINITE): a NaN or +-Inf instead sets bit 31, which
+// no |x| has, so the max over every element -- and over the ranks -- carries it
+// (deq_scale then makes every result NaN).
+template <bool NF = false>
+__device__ __forceinline__ uint32_t abs_bits(uint32_t b)
+{
+    const uint32_t a = b & 0x7fffffffu;
+    if constexpr (NF) return a >= 0x7f800000u ? 0x80000000u | a : a;
+    else return a > 0x7f800000u ? 0u : a;
+}
+
+// max |x| bits over a quad of fp32 elements
+template <bool NF>
+__device__ __forceinline__ uint32_t amax_quad(u32x4 x)
+{
+    return max(max(abs_bits<NF>(x.x), abs_bits<NF>(x.y)), max(abs_bits<NF>(x.z), abs_bits<NF>(x.w)));
+}
 
 // Tile geometry per fan-in R, from the variant sweeps on MI355X.  Round 1
 // (nontemporal stores; tools/tune/tune_stream.hip -> profiles/r01_tune_stream.jsonl,
@@ -163,17 +206,8 @@ __global__ __launch_bounds__(BLOCK) void k_stream_vec(SrcPtrs src, void* __restr
             for (int u = 0; u < U; ++u) {
                 u32x4 acc = {0u, 0u, 0u, 0u};
 #pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    acc.x += load_xform<IN>(v[r][u].x, scale);
-                    acc.y += load_xform<IN>(v[r][u].y, scale);
-                    acc.z += load_xform<IN>(v[r][u].z, scale);
-                    acc.w += load_xform<IN>(v[r][u].w, scale);
-                }
-                u32x4 o;
-                o.x = store_xform<OUT>(acc.x, inv);
-                o.y = store_xform<OUT>(acc.y, inv);
-                o.z = store_xform<OUT>(acc.z, inv);
-                o.w = store_xform<OUT>(acc.w, inv);
+                for (int r = 0; r < R; ++r) accum_quad<IN>(acc, v[r][u], scale);
+                const u32x4 o = xform_quad<OUT>(acc, inv);
                 if constexpr (SP == kStoreWT)
                     __builtin_amdgcn_raw_buffer_store_b128(o, orsrc, (int)((threadIdx.x + u * BLOCK) * 16), 0, kAuxSc1);
                 else if constexpr (SP == kStoreNT)
@@ -188,19 +222,9 @@ __global__ __launch_bounds__(BLOCK) void k_stream_vec(SrcPtrs src, void* __restr
                 if (i < n4) {
                     u32x4 acc = {0u, 0u, 0u, 0u};
 #pragma unroll
-                    for (int r = 0; r < R; ++r) {
-                        const u32x4 x = reinterpret_cast<const u32x4*>(src.p[r])[i];
-                        acc.x += load_xform<IN>(x.x, scale);
-                        acc.y += load_xform<IN>(x.y, scale);
-                        acc.z += load_xform<IN>(x.z, scale);
-                        acc.w += load_xform<IN>(x.w, scale);
-                    }
-                    u32x4 o;
-                    o.x = store_xform<OUT>(acc.x, inv);
-                    o.y = store_xform<OUT>(acc.y, inv);
-                    o.z = store_xform<OUT>(acc.z, inv);
-                    o.w = store_xform<OUT>(acc.w, inv);
-                    out[i] = o;
+                    for (int r = 0; r < R; ++r)
+                        accum_quad<IN>(acc, reinterpret_cast<const u32x4*>(src.p[r])[i], scale);
+                    out[i] = xform_quad<OUT>(acc, inv);
                 }
             }
         }

@@ -217,7 +217,7 @@ static int p2p_exchange(struct inccl_communicator *c, int in_kind, const void *c
     if (in_kind == INCCL_KIND_Q32) {
         INCCL_HIP(hipMemcpyAsync(c->p2p_part, srcs[0], n * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
     } else {
-        rc = inccl_k_stream(in_kind, INCCL_KIND_Q32, srcs, R, c->p2p_part, n, sc->k, sc->amax, sc->R, st);
+        rc = inccl_k_stream(in_kind, INCCL_KIND_Q32, srcs, R, c->p2p_part, n, sc->k, sc->amax, sc->R, 0, st);
         if (rc) return inccl_set_error(INCCL_ERR_HIP, "p2p %squant+sum launch failed (%d)",
                                        gather ? what : "reduce-scatter ", rc);
     }

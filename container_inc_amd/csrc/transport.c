@@ -220,7 +220,7 @@ int inccl_local_reduce_scatter_q32(struct inccl_communicator *c, const int32_t *
     if (rc) return rc;
     const void *srcs[INCCL_MAX_LOCAL_INPUTS];
     for (int j = 0; j < W; ++j) srcs[j] = (const int32_t *)h->send[j] + (size_t)me * shard;
-    rc = inccl_k_stream(INCCL_KIND_Q32, INCCL_KIND_Q32, srcs, W, recv, shard, 0, NULL, W, st);
+    rc = inccl_k_stream(INCCL_KIND_Q32, INCCL_KIND_Q32, srcs, W, recv, shard, 0, NULL, W, 0, st);
     int rc2 = hub_release(c, st);
     return rc ? inccl_set_error(INCCL_ERR_HIP, "local reduce-scatter kernel failed (%d)", rc) : rc2;
 }
@@ -257,7 +257,7 @@ int inccl_local_allreduce_q32(struct inccl_communicator *c, const int32_t *send,
     if (rc) return rc;
     const void *srcs[INCCL_MAX_LOCAL_INPUTS];
     for (int j = 0; j < W; ++j) srcs[j] = h->send[j];
-    rc = inccl_k_stream(INCCL_KIND_Q32, INCCL_KIND_Q32, srcs, W, c->d_q32, n, 0, NULL, W, st);
+    rc = inccl_k_stream(INCCL_KIND_Q32, INCCL_KIND_Q32, srcs, W, c->d_q32, n, 0, NULL, W, 0, st);
     int rc2 = hub_release(c, st);
     if (rc) return inccl_set_error(INCCL_ERR_HIP, "local allreduce kernel failed (%d)", rc);
     if (rc2) return rc2;

@@ -1,7 +1,10 @@
-/* scale_rule.c -- the integer form of the auto scale rule that the per-block
- * kernels run (csrc/inccl_scale_rule.h inccl_scale_of_word) against the
- * oracle's double-precision one (oracle/inccl_oracle.c orc_choose_scale), which
- * is the spec.  Words: every exponent field with the significands where the
+/* scale_rule.c -- the integer form of the auto scale rule that every kernel
+ * and the host run (csrc/inccl_scale_rule.h) against the oracle's
+ * double-precision one (oracle/inccl_oracle.c orc_choose_scale), which is the
+ * spec: inccl_scale_of_word on the word's magnitude (the per-block kernels),
+ * inccl_scale_of_float on the magnitude as a float (inccl_choose_scale), and
+ * inccl_scale_of_device_word against the oracle on the WHOLE word read as a
+ * float, flagged words included (what the single-scale kernels resolve).  Words: every exponent field with the significands where the
  * rule can turn (all zeros, all ones, one bit, the patterns next to a power of
  * two and to 2^j / R), the zero, the subnormals, Inf and NaNs, each with and
  * without bit 31, then a fixed pseudo-random sweep; R: 1..64 and larger worlds.
@@ -24,6 +27,36 @@ static void check(uint32_t word, int R)
     const int want = orc_choose_scale(amax, R), got = inccl_scale_of_word(word, R);
     ++cases;
     if (want != got && ++bad <= 20) printf("MISMATCH word %08x R %d: %d, the oracle says %d\n", word, R, got, want);
+    const int gotf = inccl_scale_of_float(amax, R);
+    if (want != gotf && ++bad <= 20) printf("MISMATCH float %08x R %d: %d, the oracle says %d\n", bits, R, gotf, want);
+    float whole;
+    memcpy(&whole, &word, sizeof(whole));
+    const int wantd = orc_choose_scale(whole, R), gotd = inccl_scale_of_device_word(word, R);
+    if (wantd != gotd && ++bad <= 20)
+        printf("MISMATCH device word %08x R %d: %d, the oracle says %d\n", word, R, gotd, wantd);
+}
+
+/* the float entry where no absmax word goes: -0, negative values, -Inf, NaNs */
+static void check_float(float amax, int R)
+{
+    const int want = orc_choose_scale(amax, R), got = inccl_scale_of_float(amax, R);
+    ++cases;
+    if (want != got && ++bad <= 20) printf("MISMATCH float %g R %d: %d, the oracle says %d\n", (double)amax, R, got, want);
+}
+
+/* R <= 0 counts as one contributor */
+static void check_r_floor(uint32_t word)
+{
+    float amax;
+    memcpy(&amax, &word, sizeof(amax));
+    for (int R = -3; R <= 0; R += 3) {
+        ++cases;
+        if ((inccl_scale_of_float(amax, R) != inccl_scale_of_float(amax, 1) ||
+             inccl_scale_of_device_word(word, R) != inccl_scale_of_device_word(word, 1) ||
+             inccl_scale_of_word(word, R) != inccl_scale_of_word(word, 1)) &&
+            ++bad <= 20)
+            printf("MISMATCH word %08x: R %d is not R 1\n", word, R);
+    }
 }
 
 int main(void)
@@ -55,7 +88,12 @@ int main(void)
             s = s * 1664525u + 1013904223u;
             check(s ^ (s >> 15), R);
         }
+        static const float odd[] = {-0.0f, -1.0f, -1e-45f, -3e38f, -0.75f, -INFINITY, NAN, -NAN};
+        for (size_t i = 0; i < sizeof(odd) / sizeof(odd[0]); ++i) check_float(odd[i], R);
     }
+    for (uint32_t e = 0; e < 256; ++e)
+        for (size_t si = 0; si < sizeof(sig) / sizeof(sig[0]); ++si)
+            for (uint32_t flag = 0; flag < 2; ++flag) check_r_floor(flag << 31 | e << 23 | sig[si]);
     printf("scale rule %s: %ld cases, %ld mismatches\n", bad ? "FAILED" : "ok", cases, bad);
     return bad ? 1 : 0;
 }

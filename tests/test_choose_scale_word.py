@@ -31,6 +31,34 @@ def test_word_rule_matches_the_float_rule_and_the_oracle(lib, orc):
         inccl.choose_scale_word(-1, 2)
 
 
+def test_auto_rule_word_list_covers_the_rule(orc):
+    """The words of the GPU test of the kernels' rule (test_gpu_kernels.py
+    test_auto_rule_from_device_word), through the oracle alone: both clamps,
+    exponents between them, and both branches of the rule (m == 0.5 or not)."""
+    import math
+
+    import auto_rule_words as arw
+    from container_inc_amd import inccl
+    pairs = [(w, R) for R in arw.RS for w in arw.words(R)]
+    assert len(pairs) <= 660 and len(set(pairs)) > 600
+    assert sum(1 for w, _ in pairs if w & arw.FLAG) >= len(pairs) // 8
+    ks, half, other = set(), 0, 0
+    for w, R in pairs:
+        if w & arw.FLAG:
+            continue
+        amax = float(arw.as_float(w))
+        k = orc.choose_scale(amax, R)
+        ks.add(k)
+        if inccl.SCALE_MIN < k < inccl.SCALE_MAX:
+            m, e = math.frexp(amax * R)
+            assert k == (31 - e if m == 0.5 else 30 - e), (hex(w), R)
+            half += m == 0.5
+            other += m != 0.5
+    assert inccl.SCALE_MIN in ks and inccl.SCALE_MAX in ks
+    assert len([k for k in ks if inccl.SCALE_MIN < k < inccl.SCALE_MAX]) > 20
+    assert half >= 20 and other >= 20, (half, other)
+
+
 def test_block_words_give_the_reference_exponents(lib, orc):
     """Per block of a mixed-magnitude bucket (and one poisoned block): the
     library's exponent of every block word is the reference's k_b."""

@@ -149,6 +149,67 @@ def test_absmax_and_auto_scale(gpu, orc, R, shift):
     _bits_equal(_np(inccl.reduce_f32_auto(ts)), orc.reduce_f32(xs, k))
 
 
+def test_auto_rule_from_device_word(gpu, orc):
+    """The exponent every single-scale kernel resolves from a device absmax word
+    is the oracle's rule on that word read as a float: for the words of
+    tests/auto_rule_words.py (both clamps, both branches of the rule, 2^j / R and
+    its neighbours, 0, Inf, NaN) the quad and the element kernels of the 4-byte
+    and the 2-byte families quantise and dequantise bit for bit as the oracle
+    does at k = choose_scale(float32(word), R).  A word with bit 31 quantises at
+    SCALE_MAX and dequantises to NaN."""
+    import torch
+
+    import auto_rule_words as arw
+    from container_inc_amd import inccl
+    pairs = [(w, R) for R in arw.RS for w in arw.words(R)]
+    P = len(pairs)
+    q = np.array([1, -1, 3, 2 ** 20 + 1, INT32_MIN, INT32_MAX, 5, 7], np.int32)
+    unit = np.array([1, -1, 0.5, 1 / 3, 2, 0, 1e-3, 0], np.float32)
+    tiny = (2.0 ** -64 * np.array([1, 3, -5, 7, 0, 2, -1, 9])).astype(np.float32)
+    h = orc.f32_to_bf16(np.array([1, -1, 0.5, 3, 2.0 ** -20, -2.0 ** 20, 1e-3, 0, 255, -7, 2.0 ** -60, 2.0 ** 60, 1.5,
+                                  -0.375, 100, -1e-10], np.float32))
+    x = np.empty((P, 8), np.float32)   # a row per pair: amax * unit, or the flagged words' tiny values
+    with np.errstate(all="ignore"):
+        for i, (w, _) in enumerate(pairs):
+            x[i] = tiny if w & arw.FLAG else arw.as_float(w) * unit
+    words_t = _t(np.array([w for w, _ in pairs], np.uint32).view(np.int32), gpu)
+    q_t, x_t = _t(q, gpu), _t(x, gpu)
+    h_t = _t(h.view(np.int16), gpu).view(torch.bfloat16)
+    deq8 = torch.zeros((P, 8), dtype=torch.float32, device=gpu)
+    deq7 = torch.zeros((P, 8), dtype=torch.float32, device=gpu)
+    qx = torch.zeros((P, 8), dtype=torch.int32, device=gpu)
+    qh16 = torch.zeros((P, 16), dtype=torch.int32, device=gpu)
+    qh15 = torch.zeros((P, 16), dtype=torch.int32, device=gpu)
+    for i, (w, R) in enumerate(pairs):
+        word = words_t[i:i + 1]
+        inccl.stream_op(inccl.KIND_Q32, inccl.KIND_F32, [q_t], deq8[i], n=8, amax_word=word, scale_R=R)
+        if w & arw.FLAG:
+            inccl.stream_op(inccl.KIND_F32, inccl.KIND_Q32, [x_t[i]], qx[i], n=8, amax_word=word, scale_R=R)
+            continue
+        inccl.stream_op(inccl.KIND_Q32, inccl.KIND_F32, [q_t], deq7[i], n=7, amax_word=word, scale_R=R)
+        inccl.stream_op(inccl.KIND_F32, inccl.KIND_Q32, [x_t[i]], qx[i], n=7, amax_word=word, scale_R=R)
+        inccl.stream_op(inccl.KIND_BF16, inccl.KIND_Q32, [h_t], qh16[i], n=16, amax_word=word, scale_R=R)
+        inccl.stream_op(inccl.KIND_BF16, inccl.KIND_Q32, [h_t], qh15[i], n=15, amax_word=word, scale_R=R)
+    torch.cuda.synchronize()
+    deq8, deq7, qx, qh16, qh15 = (t.cpu().numpy() for t in (deq8, deq7, qx, qh16, qh15))
+    by_k = {}   # the oracle's fixed-input answers, once per exponent
+    for i, (w, R) in enumerate(pairs):
+        if w & arw.FLAG:
+            np.testing.assert_array_equal(qx[i], orc.quantise(tiny, inccl.SCALE_MAX), err_msg=f"{w:#x} R {R}")
+            assert np.isnan(deq8[i]).all(), (hex(w), R)
+            continue
+        k = orc.choose_scale(float(arw.as_float(w)), R)
+        if k not in by_k:
+            by_k[k] = (orc.dequantise(q, k), orc.quant_sum_bf16([h], k))
+        want_deq, want_h = by_k[k]
+        _bits_equal(deq8[i], want_deq)
+        _bits_equal(deq7[i][:7], want_deq[:7])
+        np.testing.assert_array_equal(qx[i][:7], orc.quantise(x[i][:7], k), err_msg=f"{w:#x} R {R} k {k}")
+        np.testing.assert_array_equal(qh16[i], want_h, err_msg=f"{w:#x} R {R} k {k}")
+        np.testing.assert_array_equal(qh15[i][:15], want_h[:15], err_msg=f"{w:#x} R {R} k {k}")
+        assert deq7[i][7] == 0 and qx[i][7] == 0 and qh15[i][15] == 0   # nothing written past n
+
+
 @pytest.mark.parametrize("n", [1, 4, 1000, 1 << 20])
 def test_checksum(gpu, orc, n):
     from container_inc_amd import inccl

@@ -32,32 +32,12 @@ __global__ void k_fill(float* p, int64_t n, uint32_t seed)
     }
 }
 
-__device__ __forceinline__ uint32_t abs_bits(uint32_t b)
-{
-    const uint32_t a = b & 0x7fffffffu;
-    return a > 0x7f800000u ? 0u : a;
-}
-
-__device__ __forceinline__ uint32_t amax4(u32x4 x)
-{
-    return max(max(abs_bits(x.x), abs_bits(x.y)), max(abs_bits(x.z), abs_bits(x.w)));
-}
-
-__device__ __forceinline__ uint32_t wave_max(uint32_t v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const uint32_t o = (uint32_t)__shfl_xor((int)v, off, 64);
-        v = v > o ? v : o;
-    }
-    return v;
-}
-
+// abs_bits, amax_quad and wave_max_u32: the product's, from inccl_stream.h
 template <int BLOCK>
 __device__ __forceinline__ void block_max_atomic(uint32_t m, uint32_t* out)
 {
     __shared__ uint32_t part[BLOCK / 64];
-    m = wave_max(m);
+    m = wave_max_u32(m);
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = m;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -88,7 +68,7 @@ __global__ __launch_bounds__(BLOCK) void k_amax(SrcPtrs src, int64_t n4, uint32_
         for (int r = 0; r < R; ++r)
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                const uint32_t a = amax4(v[r][u]);
+                const uint32_t a = amax_quad<false>(v[r][u]);
                 m = m > a ? m : a;
             }
     }
