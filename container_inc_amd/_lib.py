@@ -45,6 +45,10 @@ SIGNATURES = {
     "inccl_block_absmax_f32": (_I, [_P, _I, _SZ, _P, _I, _P]),
     "inccl_reduce_f32_block": (_I, [_P, _I, _P, _SZ, _P, _I, _P]),
     "inccl_reduce_f32_block16": (_I, [_P, _I, _P, _SZ, _P, _I, _P]),
+    "inccl_block_absmax_f32_ef": (_I, [_P, _P, _I, _SZ, _P, _I, _P]),
+    "inccl_pack_f32_block16_ef": (_I, [_P, _P, _I, _P, _SZ, _P, _SZ, _I, _P]),
+    "inccl_reduce_f32_block16_ef": (_I, [_P, _P, _I, _P, _SZ, _P, _I, _P]),
+    "inccl_allreduce_f32_ef": (_I, [_P, _P, _P, _I, _P, _SZ, _P]),
     "inccl_stream_op_block": (_I, [_I, _I, _P, _I, _P, _SZ, _P, _SZ, _I, _P]),
     "inccl_checksum_q32": (_I, [_P, _SZ, _U64, _P, _I, _P]),
     "inccl_choose_scale": (_I, [_F, _I]),

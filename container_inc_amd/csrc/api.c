@@ -130,6 +130,38 @@ int inccl_reduce_f32_block16(const float *const *srcs_dev, int R, float *dst_dev
     return kerr(inccl_k_block_fused((const void *const *)srcs_dev, R, dst_dev, n, words_out_dev, flags, R, 0, 1, stream));
 }
 
+/* ---- error feedback for the packed lanes, stateless (include/inccl_amd.h) ---- */
+int inccl_block_absmax_f32_ef(const float *const *srcs_dev, const float *const *residuals_dev, int R, size_t n,
+                              uint32_t *words_dev, int flags, void *stream)
+{
+    if (!srcs_dev) return inccl_set_error(INCCL_ERR_ARG, "srcs is NULL");
+    if (!residuals_dev) return inccl_set_error(INCCL_ERR_ARG, "residuals is NULL");
+    return kerr(inccl_k_block_absmax_ef((const void *const *)srcs_dev, residuals_dev, R, n, words_dev, flags, stream));
+}
+
+int inccl_pack_f32_block16_ef(const float *const *srcs_dev, float *const *residuals_dev, int R, int32_t *dst_words_dev,
+                              size_t n, const uint32_t *words_dev, size_t elem_base, int scale_R, void *stream)
+{
+    if (!srcs_dev) return inccl_set_error(INCCL_ERR_ARG, "srcs is NULL");
+    if (!residuals_dev) return inccl_set_error(INCCL_ERR_ARG, "residuals is NULL");
+    if (scale_R < 0) return inccl_set_error(INCCL_ERR_ARG, "inccl_pack_f32_block16_ef: scale_R %d is negative", scale_R);
+    if (elem_base & 1)
+        return inccl_set_error(INCCL_ERR_ARG, "inccl_pack_f32_block16_ef: F32 -> P16 at an odd elem_base %zu (a word "
+                               "holds elements 2j and 2j + 1 of the bucket)", elem_base);
+    return kerr(inccl_k_pack_block16_ef((const void *const *)srcs_dev, residuals_dev, R, dst_words_dev, n, words_dev,
+                                        (elem_base + n + INCCL_BLOCK_ELEMS - 1) / INCCL_BLOCK_ELEMS, elem_base, scale_R,
+                                        stream));
+}
+
+int inccl_reduce_f32_block16_ef(const float *const *srcs_dev, float *const *residuals_dev, int R, float *dst_dev,
+                                size_t n, uint32_t *words_out_dev, int flags, void *stream)
+{
+    if (!srcs_dev) return inccl_set_error(INCCL_ERR_ARG, "srcs is NULL");
+    if (!residuals_dev) return inccl_set_error(INCCL_ERR_ARG, "residuals is NULL");
+    return kerr(inccl_k_block_fused_ef((const void *const *)srcs_dev, residuals_dev, R, dst_dev, n, words_out_dev, flags,
+                                       R, 0, stream));
+}
+
 int inccl_stream_op_block(int in_kind, int out_kind, const void *const *srcs_dev, int R, void *dst_dev, size_t n,
                           const uint32_t *words_dev, size_t elem_base, int scale_R, void *stream)
 {
@@ -959,7 +991,9 @@ static int resolve_block_scale(struct inccl_communicator *c, const void *const *
     if (rc) return rc;
     uint32_t *words = (uint32_t *)c->d_bwords, *rows = words + agreed;
     INCCL_HIP(hipMemsetAsync(words, 0, (agreed + (gather ? (size_t)W * nb : 0)) * sizeof(uint32_t), st));
-    rc = kerr(inccl_k_block_absmax(srcs, R, n, gather ? rows + (size_t)me * nb : words, flags, st));
+    uint32_t *own = gather ? rows + (size_t)me * nb : words;
+    rc = sc->ef ? kerr(inccl_k_block_absmax_ef(srcs, (const float *const *)sc->ef, R, n, own, flags, st))
+                : kerr(inccl_k_block_absmax(srcs, R, n, own, flags, st));
     if (rc) return rc;
     if (gather) {
         rc = inccl_tp_allreduce_q32(c, (const int32_t *)rows, (int32_t *)rows, (size_t)W * nb, st);
@@ -984,7 +1018,7 @@ static int resolve_block_scale(struct inccl_communicator *c, const void *const *
  * word, no copy back.  Otherwise the max stays on the device (sc->amax) for
  * the kernels to resolve (inccl_scale_of_device_word, the same header). */
 static int resolve_scale(struct inccl_communicator *c, int kind, const void *const *srcs, int R, size_t n,
-                         int scale_exp, hipStream_t st, struct inccl_scale *sc)
+                         int scale_exp, float *const *ef, hipStream_t st, struct inccl_scale *sc)
 {
     const int W = c->group->world_size;
     sc->k = scale_exp;
@@ -993,6 +1027,7 @@ static int resolve_scale(struct inccl_communicator *c, int kind, const void *con
     sc->blk = NULL;
     sc->nb = sc->blk_base = 0;
     sc->p16 = 0;
+    sc->ef = ef;
     if (scale_exp == INCCL_SCALE_BLOCK) {
         sc->p16 = c->wire == INCCL_WIRE_P16;
         return resolve_block_scale(c, srcs, R, n, st, sc);
@@ -1039,9 +1074,14 @@ static size_t wire_words(const struct inccl_scale *sc, size_t n) { return sc->p1
 static int quant_sum(int kind, const void *const *srcs, int R, int32_t *q, size_t n, size_t total,
                      const struct inccl_scale *sc, hipStream_t st)
 {
-    const int rc = sc->blk ? kerr(inccl_k_stream_block(kind, sc->p16 ? INCCL_KIND_P16 : INCCL_KIND_Q32, srcs, R, q, n,
-                                                       sc->blk, sc->nb, sc->blk_base, sc->R, 0, st))
-                           : kerr(inccl_k_stream(kind, INCCL_KIND_Q32, srcs, R, q, n, sc->k, sc->amax, sc->R, 0, st));
+    int rc;
+    if (sc->ef)   /* error feedback: the packed lanes of bucket + residual, the residual rewritten */
+        rc = kerr(inccl_k_pack_block16_ef(srcs, sc->ef, R, q, n, sc->blk, sc->nb, sc->blk_base, sc->R, st));
+    else if (sc->blk)
+        rc = kerr(inccl_k_stream_block(kind, sc->p16 ? INCCL_KIND_P16 : INCCL_KIND_Q32, srcs, R, q, n, sc->blk, sc->nb,
+                                       sc->blk_base, sc->R, 0, st));
+    else
+        rc = kerr(inccl_k_stream(kind, INCCL_KIND_Q32, srcs, R, q, n, sc->k, sc->amax, sc->R, 0, st));
     if (rc) return rc;
     const size_t nw = wire_words(sc, n), tw = wire_words(sc, total);
     if (tw > nw) INCCL_HIP(hipMemsetAsync(q + nw, 0, (tw - nw) * sizeof(int32_t), st));
@@ -1238,10 +1278,12 @@ static const char *const kind_names[] = {"f32", "", "", "bf16", "f16"};
  * rank's words are the agreed ones and stay in the kernel's registers).  On the
  * packed wire the kernel takes the 16-bit lanes' exponent and clamp, so that one
  * rank gives what N ranks would give. */
-static int block_fused(struct inccl_communicator *c, const void *const *srcs, int R, void *dst, size_t n,
-                       hipStream_t st)
+static int block_fused(struct inccl_communicator *c, const void *const *srcs, float *const *ef, int R, void *dst,
+                       size_t n, hipStream_t st)
 {
     const int flags = c->nonfinite == INCCL_NONFINITE_NAN ? INCCL_ABSMAX_FLAG_NONFINITE : 0;
+    if (ef)   /* error feedback: the same pass on bucket + residual, the residuals rewritten */
+        return kerr(inccl_k_block_fused_ef(srcs, ef, R, dst, n, NULL, flags, R * c->group->world_size, c->out_shift, st));
     return kerr(inccl_k_block_fused(srcs, R, dst, n, NULL, flags, R * c->group->world_size, c->out_shift,
                                     c->wire == INCCL_WIRE_P16, st));
 }
@@ -1266,8 +1308,8 @@ static int block_route(struct inccl_communicator *c, int R, size_t n, enum inccl
  * element instead of 4 (an all-gather copies bytes: the same one serves both),
  * and the mesh and p2p engines' reduce kernels narrow to the bucket's format
  * before their result exchange.  Which engine carries the bucket: inccl_route.h. */
-static int allreduce_body(struct inccl_communicator *c, int kind, const void *const *srcs, int R, void *dst, size_t n,
-                          int scale_exp, int chunks, void *stream)
+static int allreduce_body(struct inccl_communicator *c, int kind, const void *const *srcs, float *const *ef, int R,
+                          void *dst, size_t n, int scale_exp, int chunks, void *stream)
 {
     if (!c || !srcs || R < 1 || R > INCCL_MAX_LOCAL_INPUTS || (!dst && n))
         return inccl_set_error(INCCL_ERR_ARG, "bad allreduce_%s args", kind_names[kind]);
@@ -1284,10 +1326,12 @@ static int allreduce_body(struct inccl_communicator *c, int kind, const void *co
     if (block) {
         rc = block_route(c, R, n, &route);
         if (rc) return rc;
-        if (route == INCCL_ROUTE_FUSED) return block_fused(c, srcs, R, dst, n, st);
+        if (route == INCCL_ROUTE_FUSED) return block_fused(c, srcs, ef, R, dst, n, st);
+        if (ef && route != INCCL_ROUTE_AR)   /* inccl_route_packed leaves an allreduce no other route */
+            return inccl_set_error(INCCL_ERR_ARG, "inccl_allreduce_f32_ef: route %d carries no residuals", (int)route);
     }
     struct inccl_scale sc;
-    rc = resolve_scale(c, kind, srcs, R, n, scale_exp, st, &sc);
+    rc = resolve_scale(c, kind, srcs, R, n, scale_exp, ef, st, &sc);
     if (rc) return rc;
     switch (route) {
         case INCCL_ROUTE_FUSED:   /* one HBM pass: quant + sum + dequant */
@@ -1325,13 +1369,62 @@ static int allreduce_body(struct inccl_communicator *c, int kind, const void *co
 static int allreduce_any(struct inccl_communicator *c, int kind, const void *const *srcs, int R, void *dst, size_t n,
                          int scale_exp, int chunks, void *stream)
 {
-    INCCL_ORDERED(c, stream, allreduce_body(c, kind, srcs, R, dst, n, scale_exp, chunks, stream));
+    INCCL_ORDERED(c, stream, allreduce_body(c, kind, srcs, NULL, R, dst, n, scale_exp, chunks, stream));
 }
 
 int inccl_allreduce_f32(struct inccl_communicator *c, const float *const *srcs_dev, int R, float *dst_dev, size_t n,
                         int scale_exp, void *stream)
 {
     return allreduce_any(c, INCCL_KIND_F32, (const void *const *)srcs_dev, R, dst_dev, n, scale_exp, 1, stream);
+}
+
+/* [a, a + n) and [b, b + n) floats share an element */
+static int ranges_overlap(const void *a, const void *b, size_t n)
+{
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b, len = (uintptr_t)n * sizeof(float);
+    return x < y + len && y < x + len;
+}
+
+/* Error feedback (include/inccl_amd.h): everything that can be refused is
+ * refused here, before the first launch, so a failed call leaves dst and the
+ * residuals as they were.  Then the block-mode allreduce with the residuals
+ * attached in its two quantising places: the FUSED route's kernel
+ * (block_fused) and, on every other route of the packed wire (AR), the absmax
+ * (resolve_block_scale) and the quantise stage (quant_sum). */
+static int allreduce_ef_body(struct inccl_communicator *c, const float *const *srcs, float *const *res, int R,
+                             float *dst, size_t n, void *stream)
+{
+    if (!c || !srcs || R < 1 || R > INCCL_MAX_LOCAL_INPUTS || (!dst && n))
+        return inccl_set_error(INCCL_ERR_ARG, "bad allreduce_f32_ef args");
+    if (c->wire != INCCL_WIRE_P16)
+        return inccl_set_error(INCCL_ERR_ARG, "inccl_allreduce_f32_ef: error feedback belongs to the packed 16-bit "
+                               "wire; set INCCL_WIRE_P16 first (inccl_comm_set_wire)");
+    if (!res) return inccl_set_error(INCCL_ERR_ARG, "inccl_allreduce_f32_ef: residuals is NULL");
+    if ((long long)R * c->group->world_size > INCCL_P16_LANE_MAX)
+        return inccl_set_error(INCCL_ERR_ARG, "INCCL_WIRE_P16: %lld contributors exceed a 16-bit lane's %d",
+                               (long long)R * c->group->world_size, INCCL_P16_LANE_MAX);
+    for (int r = 0; r < R; ++r) {
+        if (!srcs[r] && n) return inccl_set_error(INCCL_ERR_ARG, "srcs[%d] is NULL", r);
+        if (!res[r] && n) return inccl_set_error(INCCL_ERR_ARG, "inccl_allreduce_f32_ef: residuals[%d] is NULL", r);
+    }
+    for (int r = 0; r < R && n; ++r) {
+        if (ranges_overlap(res[r], dst, n))
+            return inccl_set_error(INCCL_ERR_ARG, "inccl_allreduce_f32_ef: residuals[%d] overlaps dst", r);
+        for (int j = 0; j < R; ++j) {
+            if (ranges_overlap(res[r], srcs[j], n))
+                return inccl_set_error(INCCL_ERR_ARG, "inccl_allreduce_f32_ef: residuals[%d] overlaps srcs[%d]", r, j);
+            if (j < r && ranges_overlap(res[r], res[j], n))
+                return inccl_set_error(INCCL_ERR_ARG, "inccl_allreduce_f32_ef: residuals[%d] overlaps residuals[%d]", r,
+                                       j);
+        }
+    }
+    return allreduce_body(c, INCCL_KIND_F32, (const void *const *)srcs, res, R, dst, n, INCCL_SCALE_BLOCK, 1, stream);
+}
+
+int inccl_allreduce_f32_ef(struct inccl_communicator *c, const float *const *srcs_dev, float *const *residuals_dev,
+                           int R, float *dst_dev, size_t n, void *stream)
+{
+    INCCL_ORDERED(c, stream, allreduce_ef_body(c, srcs_dev, residuals_dev, R, dst_dev, n, stream));
 }
 
 int inccl_allreduce_f32_pipelined(struct inccl_communicator *c, const float *const *srcs_dev, int R, float *dst_dev,
@@ -1384,10 +1477,10 @@ static int reduce_scatter_body(struct inccl_communicator *c, int kind, const voi
     if (scale_exp == INCCL_SCALE_BLOCK) {
         rc = block_route(c, R, n, &route);
         if (rc) return rc;
-        if (route == INCCL_ROUTE_FUSED) return block_fused(c, srcs, R, dst, n, st);
+        if (route == INCCL_ROUTE_FUSED) return block_fused(c, srcs, NULL, R, dst, n, st);
     }
     struct inccl_scale sc;
-    rc = resolve_scale(c, kind, srcs, R, n, scale_exp, st, &sc);
+    rc = resolve_scale(c, kind, srcs, R, n, scale_exp, NULL, st, &sc);
     if (rc) return rc;
     switch (route) {
         case INCCL_ROUTE_FUSED:   /* one HBM pass */

@@ -1,5 +1,6 @@
-// inccl_block.h -- what the per-block kernels of inccl_block.hip (32-bit lanes)
-// and inccl_pack.hip (packed 16-bit lanes) share: a block's multipliers from its
+// inccl_block.h -- what the per-block kernels of inccl_block.hip (32-bit lanes),
+// inccl_pack.hip (packed 16-bit lanes) and inccl_ef.hip (those with error
+// feedback) share: a block's multipliers from its
 // word, a contribution's quantise-and-clamp and the clamped word lookup.
 #ifndef INCCL_BLOCK_H
 #define INCCL_BLOCK_H

@@ -169,7 +169,9 @@ int inccl_rccl_alltoall_q32(struct inccl_communicator *c, const int32_t *send, i
  * the piece this scale is handed to starts in the bucket, in elements.  Only
  * the stage helpers of api.c take such a scale (inccl_route_block).  p16: the
  * blocks travel as packed 16-bit lanes (INCCL_WIRE_P16), two elements an int32
- * wire word (inccl_route_packed). */
+ * wire word (inccl_route_packed).  ef: error feedback (inccl_allreduce_f32_ef),
+ * the R local buckets' residuals -- the absmax and the quantise stage then work
+ * on bucket + residual and the latter rewrites the residual; NULL otherwise. */
 struct inccl_scale {
     int k;
     const uint32_t *amax;
@@ -177,6 +179,7 @@ struct inccl_scale {
     const uint32_t *blk;
     size_t nb, blk_base;
     int p16;
+    float *const *ef;
 };
 
 /* p2p engine (p2p.c): allreduce and reduce-scatter of kind F32 / BF16 / F16

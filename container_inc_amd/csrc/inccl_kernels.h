@@ -1,5 +1,5 @@
 /* inccl_kernels.h -- the thin C-ABI shim between the C host code and the HIP
- * kernels of the seven .hip files (inccl_kernels, _block, _pack, _peer, _ll,
+ * kernels of the eight .hip files (inccl_kernels, _block, _pack, _ef, _peer, _ll,
  * _mesh; inccl_frames.hip has inccl_frames.h).  Internal to libinccl_amd.so. */
 #ifndef INCCL_KERNELS_H
 #define INCCL_KERNELS_H
@@ -44,6 +44,18 @@ int inccl_k_stream_block(int in_kind, int out_kind, const void *const *srcs, int
                          const uint32_t *words_dev, size_t nb, size_t elem_base, int scale_R, int out_shift,
                          void *stream);
 int inccl_k_words_max(const uint32_t *rows_dev, int W, size_t nb, uint32_t *out_dev, void *stream);
+/* Error feedback for the packed lanes (inccl_ef.hip; include/inccl_amd.h inccl_*_ef): res[r] is bucket
+ * r's fp32 residual, n elements beside srcs[r], none NULL.  Every kernel works on v = srcs[r] + res[r].
+ *   block_absmax_ef  block_absmax of v; the residuals are only read
+ *   pack_block16_ef  stream_block16's F32 -> P16 of v at the agreed words; res[r][i] becomes what the
+ *                    lane did not carry, 0 in a block whose word has bit 31
+ *   block_fused_ef   block_fused with p16 != 0 of v, the residuals rewritten alike */
+int inccl_k_block_absmax_ef(const void *const *srcs, const float *const *res, int R, size_t n, uint32_t *words_dev,
+                            int flags, void *stream);
+int inccl_k_pack_block16_ef(const void *const *srcs, float *const *res, int R, void *dst, size_t n,
+                            const uint32_t *words_dev, size_t nb, size_t elem_base, int scale_R, void *stream);
+int inccl_k_block_fused_ef(const void *const *srcs, float *const *res, int R, void *dst, size_t n,
+                           uint32_t *words_out_dev, int flags, int scale_R, int out_shift, void *stream);
 void inccl_k_set_tuning(int grid_cap, int nt_loads);
 /* p2p engine kernels reading peer memory with system-coherent loads (inccl_peer.hip).
  * The pull-reduce, n % 4 == 0, by out_kind:

@@ -1,6 +1,6 @@
 // inccl_launch.h -- the host side of every kernel launch, once: pointer
 // alignment, the cached CU count, the grid arithmetic, the SrcPtrs fill and the
-// dispatch on the fan-in R.  Included by all seven .hip files.
+// dispatch on the fan-in R.  Included by all eight .hip files.
 #ifndef INCCL_LAUNCH_H
 #define INCCL_LAUNCH_H
 

@@ -32,6 +32,20 @@ held a NaN or +-Inf come out NaN.  A bf16 / fp16 bucket in this mode raises.
 ``inccl_comm_set_wire``): half the exchanged bytes at 16 bits less precision per
 block, for 2-16 contributors; 32 (the default) is one int32 per element.
 
+``error_feedback=True`` (with ``scale_exp=SCALE_BLOCK`` and ``wire_bits=16``
+only, fp32 buckets) keeps what the 16-bit lanes could not carry: the hook state
+holds one fp32 residual per bucket, zero at first, which
+``Communicator.allreduce_f32_ef`` adds to the bucket before it is quantised and
+overwrites with the new remainder (``inccl_allreduce_f32_ef``).  Nothing is lost,
+it arrives a step later: the sum of T averaged gradients stays within the last
+residuals of T exact means instead of drifting by the same rounding error T
+times.  A residual belongs to ``bucket.index()`` and its size and parameter
+layout: DDP rebuilds its buckets after the first iteration, and a bucket that no
+longer matches starts from a fresh zero residual.  The residuals live on the
+communicator's stream, as the buckets' reductions do; ``reset_residuals()``
+drops them (after a skipped step or a change of the learning-rate schedule,
+where a carried remainder is unwanted).
+
 fp32, bf16 and fp16 CUDA buckets are accepted (bf16 / fp16 through
 ``inccl_allreduce_bf16`` / ``_f16``: the same int32 sums, the result rounded to
 the bucket's format).  For a power-of-two world the mean comes out of the
@@ -50,7 +64,7 @@ its communicator first, with the model still alive, crashed at exit
 from __future__ import annotations
 
 import os
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 
 from . import inccl
 from ._lib import IncclError
@@ -70,7 +84,40 @@ class HookState:
     propagate_nonfinite: bool = True   # NaN / +-Inf anywhere -> the bucket is NaN (inccl_comm_set_nonfinite)
     _nonfinite_set: bool = False
     _wire_set: bool = False
+    error_feedback: bool = False   # keep what the 16-bit lanes drop and add it to the next step (allreduce_f32_ef)
+    _residuals: dict = field(default_factory=dict, repr=False)   # (bucket index, numel) -> (layout, fp32 residual)
     wire_bits: int = 32          # 16: SCALE_BLOCK buckets travel as packed 16-bit lanes (inccl_comm_set_wire)
+
+    def __post_init__(self):
+        if self.error_feedback and (self.scale_exp != inccl.SCALE_BLOCK or self.wire_bits != 16):
+            raise IncclError("inccl hook: error_feedback=True corrects the packed 16-bit lanes: it needs "
+                             "scale_exp=SCALE_BLOCK and wire_bits=16, got "
+                             f"scale_exp={_scale_name(self.scale_exp)} and wire_bits={self.wire_bits!r}")
+
+    def residual(self, bucket, buf):
+        """The residual of this bucket, on the current stream's device memory:
+        zeros for a bucket seen for the first time or whose size or parameter
+        layout changed (DDP's rebuilt buckets); residuals of buckets past the
+        last one are dropped."""
+        import torch
+        index = bucket.index() if hasattr(bucket, "index") else 0
+        params = bucket.parameters() if hasattr(bucket, "parameters") else ()
+        layout = tuple((p.data_ptr(), p.numel()) for p in params)
+        key = (index, buf.numel())
+        held = self._residuals.get(key)
+        if held is None or held[0] != layout:
+            for k in [k for k in self._residuals if k[0] == index]:
+                del self._residuals[k]
+            held = (layout, torch.zeros(buf.numel(), dtype=torch.float32, device=buf.device))
+            self._residuals[key] = held
+        if hasattr(bucket, "is_last") and bucket.is_last():
+            for k in [k for k in self._residuals if k[0] > index]:
+                del self._residuals[k]
+        return held[1]
+
+    def reset_residuals(self) -> None:
+        """Forget every residual: the next step of each bucket starts from zero."""
+        self._residuals.clear()
 
     def fold_average(self) -> bool:
         """Once: let the engine return the mean (power-of-two worlds: 2^-log2 W is
@@ -110,10 +157,16 @@ class HookState:
         if self.scale_exp == inccl.SCALE_BLOCK and dtype != torch.float32:
             raise IncclError(f"inccl hook: scale_exp=SCALE_BLOCK (per-block auto scaling) takes fp32 gradients only, "
                              f"got {dtype}; use SCALE_AUTO for bf16 / fp16 buckets")
+        if self.error_feedback and dtype != torch.float32:
+            raise IncclError(f"inccl hook: error_feedback=True takes fp32 gradients only, got {dtype}")
 
     @property
     def world_size(self) -> int:
         return self.comm.group.world_size
+
+
+def _scale_name(k) -> str:
+    return {inccl.SCALE_AUTO: "SCALE_AUTO", inccl.SCALE_BLOCK: "SCALE_BLOCK"}.get(k, repr(k))
 
 
 def allreduce_hook(state: HookState, bucket):
@@ -146,7 +199,10 @@ def allreduce_hook(state: HookState, bucket):
         side = torch.cuda.ExternalStream(state.comm.stream, device=buf.device)
         side.wait_stream(torch.cuda.current_stream(buf.device))
         with torch.cuda.stream(side):
-            reduce([buf], out=buf, scale_exp=state.scale_exp, stream=side.cuda_stream)
+            if state.error_feedback:   # the residual is allocated on, and only touched on, `side`
+                state.comm.allreduce_f32_ef([buf], [state.residual(bucket, buf)], out=buf, stream=side.cuda_stream)
+            else:
+                reduce([buf], out=buf, scale_exp=state.scale_exp, stream=side.cuda_stream)
             if divide:
                 buf.div_(w)
             # the bucket is used on `side` now: the caching allocator must not
@@ -186,11 +242,14 @@ def communicator_from_env(port_offset: int = 17, device: int | None = None, engi
     return comm
 
 
-def register(ddp_model, comm, scale_exp: int = inccl.SCALE_AUTO, average: bool = True, wire_bits: int = 32) -> HookState:
+def register(ddp_model, comm, scale_exp: int = inccl.SCALE_AUTO, average: bool = True, wire_bits: int = 32,
+             error_feedback: bool = False) -> HookState:
     """Route every gradient bucket of ``ddp_model`` through ``comm``; returns the hook
     state.  ``scale_exp``: a fixed exponent, ``SCALE_AUTO`` (one per bucket) or
     ``SCALE_BLOCK`` (one per 256-element block, fp32 buckets; ``wire_bits=16``:
-    exchanged as packed 16-bit lanes)."""
-    state = HookState(comm=comm, scale_exp=scale_exp, average=average, wire_bits=wire_bits)
+    exchanged as packed 16-bit lanes; ``error_feedback=True`` with both: what the
+    lanes drop is kept per bucket and added to the next step)."""
+    state = HookState(comm=comm, scale_exp=scale_exp, average=average, wire_bits=wire_bits,
+                      error_feedback=error_feedback)
     ddp_model.register_comm_hook(state, allreduce_hook)
     return state

@@ -26,6 +26,8 @@ every 256-element block of the unsharded gradient on its own, shards included:
 a shard is dequantised at the exponents of the blocks it lies in, wherever it
 starts.  A bf16 / fp16 gradient in this mode raises.  ``wire_bits=16`` with it
 exchanges packed 16-bit lanes (``inccl_comm_set_wire``), as in the DDP hook.
+``error_feedback=True`` is refused: an FSDP hook sees a gradient and nothing
+that names its unit from step to step, so a residual has no stable key here.
 """
 from __future__ import annotations
 
@@ -82,7 +84,11 @@ def allreduce_hook(state: HookState, grad):
 def register(fsdp_model, comm, sharded: bool = True, **kw) -> HookState:
     """Route every FSDP unit's gradient reduction of ``fsdp_model`` through ``comm``
     (``sharded``: reduce-scatter, for the sharded strategies; else allreduce, for
-    NO_SHARD); returns the hook state.  ``kw``: HookState fields."""
+    NO_SHARD); returns the hook state.  ``kw``: HookState fields, except
+    ``error_feedback``, which only the DDP hook has."""
+    if kw.get("error_feedback"):
+        raise IncclError("inccl FSDP hook: error_feedback=True is not available: the FSDP hooks have no stable "
+                         "per-unit key to keep a residual under (use the DDP hook)")
     state = HookState(comm=comm, **kw)
     fsdp_model.register_comm_hook(state, reduce_scatter_hook if sharded else allreduce_hook)
     return state

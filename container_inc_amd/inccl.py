@@ -320,6 +320,69 @@ def reduce_f32_block16(srcs, out=None, words=None, nonfinite_flag: bool = False,
     return out
 
 
+def _ef_args(srcs, residuals):
+    """(srcs, residuals, n, source pointers, residual pointers) of an error-feedback call"""
+    torch = _torch()
+    srcs, residuals = list(srcs), list(residuals)
+    if not 1 <= len(srcs) <= MAX_LOCAL_INPUTS:
+        raise ValueError(f"1..{MAX_LOCAL_INPUTS} inputs per launch, got {len(srcs)}")
+    if len(residuals) != len(srcs):
+        raise ValueError(f"one residual per bucket: {len(srcs)} buckets, {len(residuals)} residuals")
+    n = srcs[0].numel()
+    ptrs = [_dev_ptr(s, torch.float32, f"srcs[{i}]", n) for i, s in enumerate(srcs)]
+    rptrs = [_dev_ptr(e, torch.float32, f"residuals[{i}]", n) for i, e in enumerate(residuals)]
+    return srcs, residuals, n, ptrs, rptrs
+
+
+def block_absmax_ef(srcs, residuals, words=None, nonfinite_flag: bool = False, stream=None):
+    """``block_absmax`` of ``srcs[r] + residuals[r]`` (inccl_block_absmax_f32_ef);
+    the residuals are only read."""
+    torch = _torch()
+    srcs, residuals, n, ptrs, rptrs = _ef_args(srcs, residuals)
+    if words is None:
+        words = torch.empty(_nblocks(n), dtype=torch.int32, device=srcs[0].device)
+    rc = load().inccl_block_absmax_f32_ef(_ptr_array(ptrs), _ptr_array(rptrs), len(ptrs), n,
+                                          _dev_ptr(words, torch.int32, "words", _nblocks(n)),
+                                          ABSMAX_FLAG_NONFINITE if nonfinite_flag else 0, _stream_handle(stream))
+    check(rc, "inccl_block_absmax_f32_ef")
+    return words
+
+
+def pack_block16_ef(srcs, residuals, words, out=None, elem_base: int = 0, scale_R: int = 0, stream=None):
+    """F32 -> P16 with error feedback (inccl_pack_f32_block16_ef): the packed
+    local sum of ``srcs[r] + residuals[r]`` at the agreed ``words`` (``out``:
+    ceil(n / 2) int32 words; an even ``elem_base``); every residual is
+    overwritten with what its bucket's lanes did not carry."""
+    torch = _torch()
+    srcs, residuals, n, ptrs, rptrs = _ef_args(srcs, residuals)
+    if elem_base < 0:
+        raise ValueError(f"elem_base {elem_base} is negative")
+    if out is None:
+        out = torch.empty((n + 1) // 2, dtype=torch.int32, device=srcs[0].device)
+    wptr = _dev_ptr(words, torch.int32, "words", _nblocks(int(elem_base) + n))
+    rc = load().inccl_pack_f32_block16_ef(_ptr_array(ptrs), _ptr_array(rptrs), len(ptrs),
+                                          _dev_ptr(out, torch.int32, "out", (n + 1) // 2), n, wptr, int(elem_base),
+                                          int(scale_R), _stream_handle(stream))
+    check(rc, "inccl_pack_f32_block16_ef")
+    return out
+
+
+def reduce_f32_block16_ef(srcs, residuals, out=None, words=None, nonfinite_flag: bool = False, stream=None):
+    """``reduce_f32_block16`` with error feedback (inccl_reduce_f32_block16_ef):
+    one pass over ``srcs[r] + residuals[r]``, the residuals overwritten -- what
+    the WIRE_P16 exchange of len(srcs) ranks with ``allreduce_f32_ef`` gives."""
+    torch = _torch()
+    srcs, residuals, n, ptrs, rptrs = _ef_args(srcs, residuals)
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device=srcs[0].device)
+    wptr = None if words is None else _dev_ptr(words, torch.int32, "words", _nblocks(n))
+    rc = load().inccl_reduce_f32_block16_ef(_ptr_array(ptrs), _ptr_array(rptrs), len(ptrs),
+                                            _dev_ptr(out, torch.float32, "out", n), n, wptr,
+                                            ABSMAX_FLAG_NONFINITE if nonfinite_flag else 0, _stream_handle(stream))
+    check(rc, "inccl_reduce_f32_block16_ef")
+    return out
+
+
 def stream_op_block(in_kind: int, out_kind: int, srcs, words, out=None, elem_base: int = 0, scale_R: int = 0,
                     n: int | None = None, stream=None):
     """``stream_op`` F32 -> Q32 or Q32 -> F32 at agreed per-block words
@@ -545,6 +608,29 @@ class Communicator:
 
     def allreduce_f32(self, srcs, out=None, scale_exp: int = 25, chunks: int = 1, stream=None):
         return self._allreduce("f32", srcs, out, scale_exp, stream, chunks=chunks)
+
+    def allreduce_f32_ef(self, srcs, residuals, out=None, stream=None):
+        """``allreduce_f32`` with ``SCALE_BLOCK`` on ``WIRE_P16`` with error
+        feedback (inccl_allreduce_f32_ef): ``residuals[r]`` (fp32, the size of
+        ``srcs[r]``, zeros before the first call) is added to ``srcs[r]`` and
+        overwritten with what the 16-bit lanes did not carry.  A None
+        residual reaches the library, which refuses it."""
+        torch = _torch()
+        srcs, residuals = list(srcs), list(residuals)
+        if not 1 <= len(srcs) <= MAX_LOCAL_INPUTS:
+            raise ValueError(f"1..{MAX_LOCAL_INPUTS} local buckets, got {len(srcs)}")
+        if len(residuals) != len(srcs):
+            raise ValueError(f"one residual per bucket: {len(srcs)} buckets, {len(residuals)} residuals")
+        n = srcs[0].numel()
+        ptrs = [_dev_ptr(s, torch.float32, f"srcs[{i}]", n) for i, s in enumerate(srcs)]
+        rptrs = [None if e is None else _dev_ptr(e, torch.float32, f"residuals[{i}]", n)
+                 for i, e in enumerate(residuals)]
+        if out is None:
+            out = torch.empty(n, dtype=torch.float32, device=srcs[0].device)
+        rc = load().inccl_allreduce_f32_ef(self.handle, _ptr_array(ptrs), _ptr_array(rptrs), len(ptrs),
+                                           _dev_ptr(out, torch.float32, "out", n), n, _stream_handle(stream))
+        check(rc, "inccl_allreduce_f32_ef")
+        return out
 
     def prepare_allreduce_f32(self, srcs, out=None, scale_exp: int = 25, chunks: int = 1, stream=None) -> PreparedOp:
         """``allreduce_f32`` with its arguments bound once: ``op()`` runs it."""

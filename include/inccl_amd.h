@@ -176,6 +176,43 @@ int inccl_stream_op_block(int in_kind, int out_kind, const void *const *srcs_dev
  * = R: fp32 in, fp32 out, what the packed exchange of R ranks would give. */
 int inccl_reduce_f32_block16(const float *const *srcs_dev, int R, float *dst_dev, size_t n, uint32_t *words_out_dev,
                              int flags, void *stream);
+/* ---- error feedback for the packed 16-bit lanes ----
+ * A lane drops what it cannot carry, and drops the same thing step after step.
+ * With error feedback every local bucket r has an fp32 residual e_r of n
+ * elements beside it: the caller owns it, zeroes it once, and every call reads
+ * and overwrites it.  Blocks, words, k_b, L, packing, sum and unpack are those
+ * above; they apply to v instead of x:
+ *   v_r  = fl32(x_r + e_r)                       one IEEE fp32 add, denormals kept
+ *   w_b  = the absmax word of block b over every v_r of every rank (NaN ignored;
+ *          with INCCL_ABSMAX_FLAG_NONFINITE a NaN or +-Inf in v sets bit 31)
+ *   q_r  = clamp(sat_int32(round_half_even(v_r * 2^k_b)), -L, L), NaN -> 0
+ *   y    = as above (the only place the mean's out_shift enters)
+ *   d_r  = fl32(v_r - (float)q_r * 2^-k_b)       the product is exact, so d is exact
+ *          wherever the clamp does not bind, and |d| <= 2^-(k_b + 1) there
+ *   e_r' = d_r if it is finite, else 0; and 0 for every element of a block whose
+ *          AGREED word has bit 31 set (that step is dropped on every rank, and
+ *          so is what it would have left behind)
+ * A block holding +-Inf in saturate mode has k_b = INCCL_SCALE_MIN: its +-Inf
+ * elements leave 0, its finite ones quantise to 0 and are carried whole.  Over
+ * T calls with the plain sum nothing is lost, it only arrives later:
+ *   | sum_t y_t - sum_t sum_r x_{r,t} |  <=  sum_r |e_{r,T}| + T * R_total * 2^-23 * max_t amax_b(x)
+ * (the last term: the half-ulp of each x + e), where no clamp binds and nothing
+ * is non-finite.  CPU reference: tests/block16_ef_ref.py.
+ *
+ * inccl_block_absmax_f32_ef: inccl_block_absmax_f32 of v; the residuals are only read.
+ * inccl_pack_f32_block16_ef: inccl_stream_op_block's F32 -> P16 of v at the
+ *   agreed words (dst_words_dev: ceil(n / 2) words; elem_base even; scale_R 0: R)
+ *   and residuals_dev[r][0 .. n) <- e_r'.
+ * inccl_reduce_f32_block16_ef: inccl_reduce_f32_block16 of v in one pass, the
+ *   residuals rewritten: what R ranks of one bucket each would give, bit for bit.
+ *   dst may alias srcs[0].
+ * A residual must not overlap a source, dst or another residual. */
+int inccl_block_absmax_f32_ef(const float *const *srcs_dev, const float *const *residuals_dev, int R, size_t n,
+                              uint32_t *words_dev, int flags, void *stream);
+int inccl_pack_f32_block16_ef(const float *const *srcs_dev, float *const *residuals_dev, int R, int32_t *dst_words_dev,
+                              size_t n, const uint32_t *words_dev, size_t elem_base, int scale_R, void *stream);
+int inccl_reduce_f32_block16_ef(const float *const *srcs_dev, float *const *residuals_dev, int R, float *dst_dev,
+                                size_t n, uint32_t *words_out_dev, int flags, void *stream);
 /* Position-weighted linear checksum sum_i (2(base+i)+1)*q[i] mod 2^32 into *out_dev. */
 int inccl_checksum_q32(const int32_t *q_dev, size_t n, uint64_t index_base, uint32_t *out_dev, int zero_first,
                        void *stream);
@@ -354,6 +391,16 @@ int inccl_comm_stage_times(struct inccl_communicator *comm, double *us, int kind
  * end on the device, since they share the communicator's workspaces. */
 int inccl_allreduce_f32(struct inccl_communicator *comm, const float *const *srcs_dev, int R, float *dst_dev,
                         size_t n, int scale_exp, void *stream);
+/* inccl_allreduce_f32 with INCCL_SCALE_BLOCK on the packed wire, with error
+ * feedback ("error feedback for the packed 16-bit lanes" above): residuals_dev[r]
+ * belongs to srcs_dev[r], n floats, read and overwritten.  The exchange is the
+ * packed wire's, byte for byte; the mean and the non-finite mode of the
+ * communicator apply as in block mode.  INCCL_ERR_ARG, with dst and the
+ * residuals untouched, when the communicator's wire is not INCCL_WIRE_P16, a
+ * residual pointer is NULL, a residual's n floats overlap a source, dst or
+ * another residual, or R_total > 32767.  dst may alias srcs[0]. */
+int inccl_allreduce_f32_ef(struct inccl_communicator *comm, const float *const *srcs_dev, float *const *residuals_dev,
+                           int R, float *dst_dev, size_t n, void *stream);
 /* Same with the bucket split into `chunks` pieces pipelined over two streams
  * (compute of chunk c+1 overlaps the collectives of chunk c).  chunks <= 1 is
  * inccl_allreduce_f32. */
