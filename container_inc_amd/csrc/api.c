@@ -113,21 +113,21 @@ int inccl_stream_op(int in_kind, int out_kind, const void *const *srcs_dev, int 
 int inccl_block_absmax_f32(const float *const *srcs_dev, int R, size_t n, uint32_t *words_dev, int flags, void *stream)
 {
     if (!srcs_dev) return inccl_set_error(INCCL_ERR_ARG, "srcs is NULL");
-    return kerr(inccl_k_block_absmax((const void *const *)srcs_dev, R, n, words_dev, flags, stream));
+    return kerr(inccl_k_block_absmax((const void *const *)srcs_dev, NULL, R, n, words_dev, flags, stream));
 }
 
 int inccl_reduce_f32_block(const float *const *srcs_dev, int R, float *dst_dev, size_t n, uint32_t *words_out_dev,
                            int flags, void *stream)
 {
     if (!srcs_dev) return inccl_set_error(INCCL_ERR_ARG, "srcs is NULL");
-    return kerr(inccl_k_block_fused((const void *const *)srcs_dev, R, dst_dev, n, words_out_dev, flags, R, 0, 0, stream));
+    return kerr(inccl_k_block_fused((const void *const *)srcs_dev, NULL, R, dst_dev, n, words_out_dev, flags, R, 0, 0, stream));
 }
 
 int inccl_reduce_f32_block16(const float *const *srcs_dev, int R, float *dst_dev, size_t n, uint32_t *words_out_dev,
                              int flags, void *stream)
 {
     if (!srcs_dev) return inccl_set_error(INCCL_ERR_ARG, "srcs is NULL");
-    return kerr(inccl_k_block_fused((const void *const *)srcs_dev, R, dst_dev, n, words_out_dev, flags, R, 0, 1, stream));
+    return kerr(inccl_k_block_fused((const void *const *)srcs_dev, NULL, R, dst_dev, n, words_out_dev, flags, R, 0, 1, stream));
 }
 
 /* ---- error feedback for the packed lanes, stateless (include/inccl_amd.h) ---- */
@@ -136,7 +136,7 @@ int inccl_block_absmax_f32_ef(const float *const *srcs_dev, const float *const *
 {
     if (!srcs_dev) return inccl_set_error(INCCL_ERR_ARG, "srcs is NULL");
     if (!residuals_dev) return inccl_set_error(INCCL_ERR_ARG, "residuals is NULL");
-    return kerr(inccl_k_block_absmax_ef((const void *const *)srcs_dev, residuals_dev, R, n, words_dev, flags, stream));
+    return kerr(inccl_k_block_absmax((const void *const *)srcs_dev, residuals_dev, R, n, words_dev, flags, stream));
 }
 
 int inccl_pack_f32_block16_ef(const float *const *srcs_dev, float *const *residuals_dev, int R, int32_t *dst_words_dev,
@@ -148,9 +148,10 @@ int inccl_pack_f32_block16_ef(const float *const *srcs_dev, float *const *residu
     if (elem_base & 1)
         return inccl_set_error(INCCL_ERR_ARG, "inccl_pack_f32_block16_ef: F32 -> P16 at an odd elem_base %zu (a word "
                                "holds elements 2j and 2j + 1 of the bucket)", elem_base);
-    return kerr(inccl_k_pack_block16_ef((const void *const *)srcs_dev, residuals_dev, R, dst_words_dev, n, words_dev,
-                                        (elem_base + n + INCCL_BLOCK_ELEMS - 1) / INCCL_BLOCK_ELEMS, elem_base, scale_R,
-                                        stream));
+    return kerr(inccl_k_stream_block16(INCCL_KIND_F32, INCCL_KIND_P16, (const void *const *)srcs_dev, residuals_dev, R,
+                                       dst_words_dev, n, words_dev,
+                                       (elem_base + n + INCCL_BLOCK_ELEMS - 1) / INCCL_BLOCK_ELEMS, elem_base, scale_R, 0,
+                                       stream));
 }
 
 int inccl_reduce_f32_block16_ef(const float *const *srcs_dev, float *const *residuals_dev, int R, float *dst_dev,
@@ -158,8 +159,8 @@ int inccl_reduce_f32_block16_ef(const float *const *srcs_dev, float *const *resi
 {
     if (!srcs_dev) return inccl_set_error(INCCL_ERR_ARG, "srcs is NULL");
     if (!residuals_dev) return inccl_set_error(INCCL_ERR_ARG, "residuals is NULL");
-    return kerr(inccl_k_block_fused_ef((const void *const *)srcs_dev, residuals_dev, R, dst_dev, n, words_out_dev, flags,
-                                       R, 0, stream));
+    return kerr(inccl_k_block_fused((const void *const *)srcs_dev, residuals_dev, R, dst_dev, n, words_out_dev, flags, R,
+                                    0, 1, stream));
 }
 
 int inccl_stream_op_block(int in_kind, int out_kind, const void *const *srcs_dev, int R, void *dst_dev, size_t n,
@@ -992,8 +993,7 @@ static int resolve_block_scale(struct inccl_communicator *c, const void *const *
     uint32_t *words = (uint32_t *)c->d_bwords, *rows = words + agreed;
     INCCL_HIP(hipMemsetAsync(words, 0, (agreed + (gather ? (size_t)W * nb : 0)) * sizeof(uint32_t), st));
     uint32_t *own = gather ? rows + (size_t)me * nb : words;
-    rc = sc->ef ? kerr(inccl_k_block_absmax_ef(srcs, (const float *const *)sc->ef, R, n, own, flags, st))
-                : kerr(inccl_k_block_absmax(srcs, R, n, own, flags, st));
+    rc = kerr(inccl_k_block_absmax(srcs, (const float *const *)sc->ef, R, n, own, flags, st));   /* ef or NULL */
     if (rc) return rc;
     if (gather) {
         rc = inccl_tp_allreduce_q32(c, (const int32_t *)rows, (int32_t *)rows, (size_t)W * nb, st);
@@ -1075,11 +1075,11 @@ static int quant_sum(int kind, const void *const *srcs, int R, int32_t *q, size_
                      const struct inccl_scale *sc, hipStream_t st)
 {
     int rc;
-    if (sc->ef)   /* error feedback: the packed lanes of bucket + residual, the residual rewritten */
-        rc = kerr(inccl_k_pack_block16_ef(srcs, sc->ef, R, q, n, sc->blk, sc->nb, sc->blk_base, sc->R, st));
+    if (sc->blk && sc->p16)   /* sc->ef: error feedback, the packed lanes of bucket + residual, the residual rewritten */
+        rc = kerr(inccl_k_stream_block16(kind, INCCL_KIND_P16, srcs, sc->ef, R, q, n, sc->blk, sc->nb, sc->blk_base,
+                                         sc->R, 0, st));
     else if (sc->blk)
-        rc = kerr(inccl_k_stream_block(kind, sc->p16 ? INCCL_KIND_P16 : INCCL_KIND_Q32, srcs, R, q, n, sc->blk, sc->nb,
-                                       sc->blk_base, sc->R, 0, st));
+        rc = kerr(inccl_k_stream_block(kind, INCCL_KIND_Q32, srcs, R, q, n, sc->blk, sc->nb, sc->blk_base, sc->R, 0, st));
     else
         rc = kerr(inccl_k_stream(kind, INCCL_KIND_Q32, srcs, R, q, n, sc->k, sc->amax, sc->R, 0, st));
     if (rc) return rc;
@@ -1282,9 +1282,8 @@ static int block_fused(struct inccl_communicator *c, const void *const *srcs, fl
                        size_t n, hipStream_t st)
 {
     const int flags = c->nonfinite == INCCL_NONFINITE_NAN ? INCCL_ABSMAX_FLAG_NONFINITE : 0;
-    if (ef)   /* error feedback: the same pass on bucket + residual, the residuals rewritten */
-        return kerr(inccl_k_block_fused_ef(srcs, ef, R, dst, n, NULL, flags, R * c->group->world_size, c->out_shift, st));
-    return kerr(inccl_k_block_fused(srcs, R, dst, n, NULL, flags, R * c->group->world_size, c->out_shift,
+    /* ef: error feedback, the same pass on bucket + residual, the residuals rewritten (the packed wire only) */
+    return kerr(inccl_k_block_fused(srcs, ef, R, dst, n, NULL, flags, R * c->group->world_size, c->out_shift,
                                     c->wire == INCCL_WIRE_P16, st));
 }
 

@@ -29,8 +29,23 @@
 //                                pointers not 16-B aligned)
 //   k_words_max                  element-wise unsigned max of W rows of words
 //
-// Only vector stores and plain C++.  Every lane of a wave reaches every
-// __shfl_xor: the loops and branches around them are wave-uniform.
+// Error feedback (EF, inccl_block.h) is a compile-time switch of the packed
+// lanes' kernels, not a copy of them: k_stream_block_fused, k_block_fused_elem
+// (both with P16 only) and k_block_absmax take the residuals as a parameter
+// pack RES..., empty or one ResPtrs, right after the sources.  An empty pack
+// leaves the kernel's arguments as they are without EF; a parameter of an
+// empty type would take a slot and move every later one.  With EF they work on
+// v = x + e:
+//   k_block_absmax<R, NF, ResPtrs>              the words of v, the residuals
+//                                               only read; 8 R n bytes
+//   k_stream_block_fused<R, NF, true, ResPtrs>  plus e', (12 R + 4) n bytes; the
+//                                               flagged-block rule uses the word
+//                                               the wave computed
+//   k_block_fused_elem<R, NF, true, ResPtrs>    the same per element
+//
+// Nontemporal loads of quads, vector stores (nontemporal for the residual
+// quads) and plain C++.  Every lane of a wave reaches every __shfl_xor: the
+// loops and branches around them are wave-uniform.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -40,13 +55,15 @@ namespace {
 
 using namespace inccl_dev;
 
-__device__ __forceinline__ uint32_t fused1(uint32_t acc, float inv) { return store_xform<F32>(acc, inv); }
-
-template <int R, bool NF, bool P16, int BLOCK, int U>
-__global__ __launch_bounds__(BLOCK) void k_stream_block_fused(SrcPtrs src, void* __restrict__ dst, int64_t n,
-                                                              uint32_t* __restrict__ words, int scale_R,
+// EF: every lane also writes the residual quads (and tail elements) it read
+template <int R, bool NF, bool P16, int BLOCK, int U, class... RES>
+__global__ __launch_bounds__(BLOCK) void k_stream_block_fused(SrcPtrs src, RES... res_arg, void* __restrict__ dst,
+                                                              int64_t n, uint32_t* __restrict__ words, int scale_R,
                                                               int out_shift)
 {
+    constexpr bool EF = sizeof...(RES) != 0;
+    const Res<EF> res = res_of(res_arg...);
+    static_assert(P16 || !EF, "error feedback belongs to the packed 16-bit lanes");
     const int64_t n4 = n >> 2;
     const int tail = (int)(n & 3);                    // elements after the last quad: lane i == n4 takes them
     const int64_t nq = ((n + 255) >> 8) << 6;         // quads of whole blocks: a wave for every block
@@ -64,9 +81,7 @@ __global__ __launch_bounds__(BLOCK) void k_stream_block_fused(SrcPtrs src, void*
         for (int u = 0; u < U; ++u) {
             const int64_t i = base + threadIdx.x + (int64_t)u * BLOCK;
 #pragma unroll
-            for (int r = 0; r < R; ++r)
-                v[r][u] = (full || i < n4) ? __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(src.p[r]) + i)
-                                           : u32x4{0u, 0u, 0u, 0u};
+            for (int r = 0; r < R; ++r) v[r][u] = (full || i < n4) ? ld_quad<EF>(src.p[r], res, r, i) : u32x4{0u, 0u, 0u, 0u};
         }
         __amdgpu_buffer_rsrc_t orsrc;
         if (full) orsrc = __builtin_amdgcn_make_buffer_rsrc(out + base, 0, (int)(tile * 16), 0x00020000);
@@ -87,7 +102,7 @@ __global__ __launch_bounds__(BLOCK) void k_stream_block_fused(SrcPtrs src, void*
                 for (int r = 0; r < R; ++r)
 #pragma unroll
                     for (int j = 0; j < 3; ++j) {
-                        t[r][j] = j < tail ? reinterpret_cast<const uint32_t*>(src.p[r])[n4 * 4 + j] : 0u;
+                        t[r][j] = j < tail ? ld1<EF>(src.p[r], res, r, n4 * 4 + j) : 0u;
                         const uint32_t a = abs_bits<NF>(t[r][j]);
                         m = m > a ? m : a;
                     }
@@ -95,14 +110,14 @@ __global__ __launch_bounds__(BLOCK) void k_stream_block_fused(SrcPtrs src, void*
             // the block's word, wave-uniform: the exponent is resolved once per wave
             const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max_u32(m));
             const BlockMul bm = block_mul<P16>(w, scale_R, out_shift);
+            const auto cm = contrib_mul<EF>(bm, w, scale_R);
             if (words != nullptr && lane == 0) words[i >> 6] = w;
             u32x4 acc = {0u, 0u, 0u, 0u};
 #pragma unroll
             for (int r = 0; r < R; ++r) {
-                acc.x += quantb<P16>(__uint_as_float(v[r][u].x), bm.scale, L);
-                acc.y += quantb<P16>(__uint_as_float(v[r][u].y), bm.scale, L);
-                acc.z += quantb<P16>(__uint_as_float(v[r][u].z), bm.scale, L);
-                acc.w += quantb<P16>(__uint_as_float(v[r][u].w), bm.scale, L);
+                u32x4 e;
+                contrib_quad<P16, EF>(acc, v[r][u], cm, L, &e);
+                if (full || i < n4) st_quad<EF>(res, r, i, e);
             }
             const u32x4 o = xform_quad<F32>(acc, bm.inv);
             if (full)
@@ -115,22 +130,28 @@ __global__ __launch_bounds__(BLOCK) void k_stream_block_fused(SrcPtrs src, void*
                     if (j < tail) {
                         uint32_t a = 0;
 #pragma unroll
-                        for (int r = 0; r < R; ++r) a += quantb<P16>(__uint_as_float(t[r][j]), bm.scale, L);
-                        out1[n4 * 4 + j] = fused1(a, bm.inv);
+                        for (int r = 0; r < R; ++r) {
+                            uint32_t e;
+                            a += contrib<P16, EF>(t[r][j], cm, L, &e);
+                            st1<EF>(res, r, n4 * 4 + j, e);
+                        }
+                        out1[n4 * 4 + j] = store_xform<F32>(a, bm.inv);
                     }
             }
         }
     }
 }
 
-constexpr int kBlkWaves = kBlock / 64;   // waves = blocks per workgroup and step of the per-block kernels
-
 // the fused kernel per element: lane t of the block's wave takes elements
 // 256 b + t + 64 j, j < 4 (coalesced dword accesses)
-template <int R, bool NF, bool P16>
-__global__ __launch_bounds__(kBlock) void k_block_fused_elem(SrcPtrs src, void* __restrict__ dst, int64_t n,
-                                                             uint32_t* __restrict__ words, int scale_R, int out_shift)
+template <int R, bool NF, bool P16, class... RES>
+__global__ __launch_bounds__(kBlock) void k_block_fused_elem(SrcPtrs src, RES... res_arg, void* __restrict__ dst,
+                                                             int64_t n, uint32_t* __restrict__ words, int scale_R,
+                                                             int out_shift)
 {
+    constexpr bool EF = sizeof...(RES) != 0;
+    const Res<EF> res = res_of(res_arg...);
+    static_assert(P16 || !EF, "error feedback belongs to the packed 16-bit lanes");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t nb = (n + 255) >> 8;
     const int L = P16 ? inccl_p16_clamp(scale_R) : 0;
@@ -143,7 +164,7 @@ __global__ __launch_bounds__(kBlock) void k_block_fused_elem(SrcPtrs src, void* 
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int64_t e = (b << 8) + j * 64 + lane;
-                x[r][j] = e < n ? reinterpret_cast<const uint32_t*>(src.p[r])[e] : 0u;
+                x[r][j] = e < n ? ld1<EF>(src.p[r], res, r, e) : 0u;
             }
 #pragma unroll
         for (int r = 0; r < R; ++r)
@@ -154,6 +175,7 @@ __global__ __launch_bounds__(kBlock) void k_block_fused_elem(SrcPtrs src, void* 
             }
         const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max_u32(m));
         const BlockMul bm = block_mul<P16>(w, scale_R, out_shift);
+        const auto cm = contrib_mul<EF>(bm, w, scale_R);
         if (words != nullptr && lane == 0) words[b] = w;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -161,18 +183,25 @@ __global__ __launch_bounds__(kBlock) void k_block_fused_elem(SrcPtrs src, void* 
             if (e < n) {
                 uint32_t a = 0;
 #pragma unroll
-                for (int r = 0; r < R; ++r) a += quantb<P16>(__uint_as_float(x[r][j]), bm.scale, L);
-                out[e] = fused1(a, bm.inv);
+                for (int r = 0; r < R; ++r) {
+                    uint32_t d;
+                    a += contrib<P16, EF>(x[r][j], cm, L, &d);
+                    st1<EF>(res, r, e, d);
+                }
+                out[e] = store_xform<F32>(a, bm.inv);
             }
         }
     }
 }
 
-// words[b] = max |x| bits over block b of the R buckets; vec: every bucket is 16-B aligned
-template <int R, bool NF>
-__global__ __launch_bounds__(kBlock) void k_block_absmax(SrcPtrs src, int64_t n, uint32_t* __restrict__ words,
-                                                         int vec)
+// words[b] = max |v| bits over block b of the R buckets; vec: every pointer is
+// 16-B aligned.  EF: the residuals are only read
+template <int R, bool NF, class... RES>
+__global__ __launch_bounds__(kBlock) void k_block_absmax(SrcPtrs src, RES... res_arg, int64_t n,
+                                                         uint32_t* __restrict__ words, int vec)
 {
+    constexpr bool EF = sizeof...(RES) != 0;
+    const Res<EF> res = res_of(res_arg...);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t nb = (n + 255) >> 8, n4 = n >> 2;
     const int tail = (int)(n & 3);
@@ -183,8 +212,7 @@ __global__ __launch_bounds__(kBlock) void k_block_absmax(SrcPtrs src, int64_t n,
             if (i < n4) {
                 u32x4 v[R];
 #pragma unroll
-                for (int r = 0; r < R; ++r)
-                    v[r] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(src.p[r]) + i);
+                for (int r = 0; r < R; ++r) v[r] = ld_quad<EF>(src.p[r], res, r, i);
 #pragma unroll
                 for (int r = 0; r < R; ++r) {
                     const uint32_t a = amax_quad<NF>(v[r]);
@@ -194,7 +222,7 @@ __global__ __launch_bounds__(kBlock) void k_block_absmax(SrcPtrs src, int64_t n,
 #pragma unroll
                 for (int r = 0; r < R; ++r)
                     for (int j = 0; j < tail; ++j) {
-                        const uint32_t a = abs_bits<NF>(reinterpret_cast<const uint32_t*>(src.p[r])[n4 * 4 + j]);
+                        const uint32_t a = abs_bits<NF>(ld1<EF>(src.p[r], res, r, n4 * 4 + j));
                         m = m > a ? m : a;
                     }
             }
@@ -204,7 +232,7 @@ __global__ __launch_bounds__(kBlock) void k_block_absmax(SrcPtrs src, int64_t n,
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int64_t e = (b << 8) + j * 64 + lane;
-                    const uint32_t a = e < n ? abs_bits<NF>(reinterpret_cast<const uint32_t*>(src.p[r])[e]) : 0u;
+                    const uint32_t a = e < n ? abs_bits<NF>(ld1<EF>(src.p[r], res, r, e)) : 0u;
                     m = m > a ? m : a;
                 }
         }
@@ -267,27 +295,39 @@ __global__ __launch_bounds__(kBlock) void k_words_max(const uint32_t* __restrict
 // ---------------------------------------------------------------------------
 // host-side dispatch
 // ---------------------------------------------------------------------------
+// e: the residuals or NULL; they imply the packed lanes (the shim refuses them otherwise)
 template <int R, bool NF, bool P16>
-void launch_fused(const SrcPtrs& s, void* dst, int64_t n, uint32_t* words, int scale_R, int out_shift, bool vec,
-                  hipStream_t st)
+void launch_fused(const SrcPtrs& s, const ResPtrs* e, void* dst, int64_t n, uint32_t* words, int scale_R,
+                  int out_shift, bool vec, hipStream_t st)
 {
     const int64_t nb = (n + 255) >> 8;
     if (vec) {
         constexpr int B = Geometry<R>::BLOCK, U = Geometry<R>::U;
         // one workgroup per tile, as the single-scale fused kernel
-        hipLaunchKernelGGL((k_stream_block_fused<R, NF, P16, B, U>), dim3(grid_capped(nb * 64, B * U, kNoCap)), dim3(B), 0,
-                           st, s, dst, n, words, scale_R, out_shift);
+        const dim3 grid(grid_capped(nb * 64, B * U, kNoCap));
+        if (e)
+            hipLaunchKernelGGL((k_stream_block_fused<R, NF, true, B, U, ResPtrs>), grid, dim3(B), 0, st, s, *e, dst, n,
+                               words, scale_R, out_shift);
+        else
+            hipLaunchKernelGGL((k_stream_block_fused<R, NF, P16, B, U>), grid, dim3(B), 0, st, s, dst, n, words, scale_R,
+                               out_shift);
     } else {
-        hipLaunchKernelGGL((k_block_fused_elem<R, NF, P16>), dim3(grid_of(nb, kBlkWaves, 8)), dim3(kBlock), 0, st, s, dst, n,
-                           words, scale_R, out_shift);
+        const dim3 grid(grid_of(nb, kBlkWaves, 8));
+        if (e)
+            hipLaunchKernelGGL((k_block_fused_elem<R, NF, true, ResPtrs>), grid, dim3(kBlock), 0, st, s, *e, dst, n, words,
+                               scale_R, out_shift);
+        else
+            hipLaunchKernelGGL((k_block_fused_elem<R, NF, P16>), grid, dim3(kBlock), 0, st, s, dst, n, words, scale_R,
+                               out_shift);
     }
 }
 
 template <int R, bool NF>
-void launch_absmax(const SrcPtrs& s, int64_t n, uint32_t* words, bool vec, hipStream_t st)
+void launch_absmax(const SrcPtrs& s, const ResPtrs* e, int64_t n, uint32_t* words, bool vec, hipStream_t st)
 {
-    hipLaunchKernelGGL((k_block_absmax<R, NF>), dim3(grid_of((n + 255) >> 8, kBlkWaves, 8)), dim3(kBlock), 0, st, s, n,
-                       words, vec ? 1 : 0);
+    const dim3 grid(grid_of((n + 255) >> 8, kBlkWaves, 8));
+    if (e) hipLaunchKernelGGL((k_block_absmax<R, NF, ResPtrs>), grid, dim3(kBlock), 0, st, s, *e, n, words, vec ? 1 : 0);
+    else hipLaunchKernelGGL((k_block_absmax<R, NF>), grid, dim3(kBlock), 0, st, s, n, words, vec ? 1 : 0);
 }
 
 template <int IN, int OUT, int R>
@@ -312,36 +352,40 @@ void launch_stream(const SrcPtrs& s, void* dst, int64_t n, const uint32_t* words
 
 extern "C" {
 
-int inccl_k_block_absmax(const void* const* srcs, int R, size_t n, uint32_t* words_dev, int flags, void* stream)
+int inccl_k_block_absmax(const void* const* srcs, const float* const* res, int R, size_t n, uint32_t* words_dev,
+                         int flags, void* stream)
 {
     SrcPtrs s;
+    ResPtrs e;   // only read here
     bool vec = true;
-    if (fill_srcs(srcs, R, &s, &vec) || (flags & ~INCCL_ABSMAX_FLAG_NONFINITE) || (words_dev == nullptr && n > 0))
+    if (fill_srcs(srcs, R, &s, &vec) || (res != nullptr && fill_srcs(const_cast<float* const*>(res), R, &e, &vec)) ||
+        (flags & ~INCCL_ABSMAX_FLAG_NONFINITE) || (words_dev == nullptr && n > 0))
         return INCCL_ERR_ARG;
     if (n == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
-#define INCCL_CALL(RR)                                                       \
-    if (flags) launch_absmax<RR, true>(s, (int64_t)n, words_dev, vec, st);  \
-    else launch_absmax<RR, false>(s, (int64_t)n, words_dev, vec, st)
+#define INCCL_CALL(RR)                                                                            \
+    if (flags) launch_absmax<RR, true>(s, res ? &e : nullptr, (int64_t)n, words_dev, vec, st);    \
+    else launch_absmax<RR, false>(s, res ? &e : nullptr, (int64_t)n, words_dev, vec, st)
     INCCL_R_SWITCH(R, INCCL_CALL)
 #undef INCCL_CALL
     return (int)hipGetLastError();
 }
 
-int inccl_k_block_fused(const void* const* srcs, int R, void* dst, size_t n, uint32_t* words_out_dev, int flags,
-                        int scale_R, int out_shift, int p16, void* stream)
+int inccl_k_block_fused(const void* const* srcs, float* const* res, int R, void* dst, size_t n,
+                        uint32_t* words_out_dev, int flags, int scale_R, int out_shift, int p16, void* stream)
 {
     SrcPtrs s;
+    ResPtrs e;
     bool vec = aligned16(dst);
-    if (fill_srcs(srcs, R, &s, &vec) || (flags & ~INCCL_ABSMAX_FLAG_NONFINITE) || (dst == nullptr && n > 0) ||
-        out_shift < 0 || out_shift > 8)
+    if (fill_srcs(srcs, R, &s, &vec) || (res != nullptr && (!p16 || fill_srcs(res, R, &e, &vec))) ||
+        (flags & ~INCCL_ABSMAX_FLAG_NONFINITE) || (dst == nullptr && n > 0) || out_shift < 0 || out_shift > 8)
         return INCCL_ERR_ARG;
     if (scale_R <= 0) scale_R = R;
     if (p16 && scale_R > INCCL_P16_LANE_MAX) return INCCL_ERR_ARG;
     if (n == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
 #define INCCL_FUSED(RR, NF, P)                                                                            \
-    launch_fused<RR, NF, P>(s, dst, (int64_t)n, words_out_dev, scale_R, out_shift, vec, st)
+    launch_fused<RR, NF, P>(s, res ? &e : nullptr, dst, (int64_t)n, words_out_dev, scale_R, out_shift, vec, st)
 #define INCCL_CALL(RR)                                                                                    \
     if (p16) {                                                                                            \
         if (flags) INCCL_FUSED(RR, true, true);                                                           \
@@ -359,8 +403,8 @@ int inccl_k_stream_block(int in_kind, int out_kind, const void* const* srcs, int
                          void* stream)
 {
     if (in_kind == P16 || out_kind == P16)   // packed 16-bit lanes: inccl_pack.hip
-        return inccl_k_stream_block16(in_kind, out_kind, srcs, R, dst, n, words_dev, nb, elem_base, scale_R, out_shift,
-                                      stream);
+        return inccl_k_stream_block16(in_kind, out_kind, srcs, nullptr, R, dst, n, words_dev, nb, elem_base, scale_R,
+                                      out_shift, stream);
     SrcPtrs s;
     bool vec = aligned16(dst);
     const bool quant = in_kind == F32 && out_kind == Q32, deq = in_kind == Q32 && out_kind == F32;

@@ -1,5 +1,5 @@
 /* inccl_kernels.h -- the thin C-ABI shim between the C host code and the HIP
- * kernels of the eight .hip files (inccl_kernels, _block, _pack, _ef, _peer, _ll,
+ * kernels of the seven .hip files (inccl_kernels, _block, _pack, _peer, _ll,
  * _mesh; inccl_frames.hip has inccl_frames.h).  Internal to libinccl_amd.so. */
 #ifndef INCCL_KERNELS_H
 #define INCCL_KERNELS_H
@@ -33,29 +33,25 @@ int inccl_k_checksum(const int32_t *q, size_t n, uint64_t index_base, uint32_t *
  * Packed 16-bit lanes (INCCL_KIND_P16; inccl_pack.hip): block_fused with p16 != 0 takes the lanes'
  * exponent and clamp; stream_block also takes F32 -> P16 (dst: ceil(n / 2) words, elem_base even) and
  * P16 -> F32 (n: elements of dst; srcs point at the word that holds element elem_base) and hands them
- * to stream_block16.  scale_R above INCCL_P16_LANE_MAX is INCCL_ERR_ARG. */
-int inccl_k_block_absmax(const void *const *srcs, int R, size_t n, uint32_t *words_dev, int flags, void *stream);
-int inccl_k_block_fused(const void *const *srcs, int R, void *dst, size_t n, uint32_t *words_out_dev, int flags,
-                        int scale_R, int out_shift, int p16, void *stream);
-int inccl_k_stream_block16(int in_kind, int out_kind, const void *const *srcs, int R, void *dst, size_t n,
-                           const uint32_t *words_dev, size_t nb, size_t elem_base, int scale_R, int out_shift,
-                           void *stream);
+ * to stream_block16.  scale_R above INCCL_P16_LANE_MAX is INCCL_ERR_ARG.
+ * Error feedback for the packed lanes (include/inccl_amd.h inccl_*_ef): res is NULL (none) or R fp32
+ * residuals, res[r] n elements beside srcs[r], none NULL; the kernel then works on v = srcs[r] + res[r].
+ * A res that is not NULL belongs to the packed lanes only (block_fused: p16 != 0; stream_block16:
+ * F32 -> P16), INCCL_ERR_ARG otherwise.
+ *   block_absmax    of v; the residuals are only read
+ *   block_fused     of v; res[r][i] becomes what the lane did not carry, 0 in a block whose word has bit 31
+ *   stream_block16  F32 -> P16 of v at the agreed words, the residuals rewritten alike */
+int inccl_k_block_absmax(const void *const *srcs, const float *const *res, int R, size_t n, uint32_t *words_dev,
+                         int flags, void *stream);
+int inccl_k_block_fused(const void *const *srcs, float *const *res, int R, void *dst, size_t n,
+                        uint32_t *words_out_dev, int flags, int scale_R, int out_shift, int p16, void *stream);
+int inccl_k_stream_block16(int in_kind, int out_kind, const void *const *srcs, float *const *res, int R, void *dst,
+                           size_t n, const uint32_t *words_dev, size_t nb, size_t elem_base, int scale_R,
+                           int out_shift, void *stream);
 int inccl_k_stream_block(int in_kind, int out_kind, const void *const *srcs, int R, void *dst, size_t n,
                          const uint32_t *words_dev, size_t nb, size_t elem_base, int scale_R, int out_shift,
                          void *stream);
 int inccl_k_words_max(const uint32_t *rows_dev, int W, size_t nb, uint32_t *out_dev, void *stream);
-/* Error feedback for the packed lanes (inccl_ef.hip; include/inccl_amd.h inccl_*_ef): res[r] is bucket
- * r's fp32 residual, n elements beside srcs[r], none NULL.  Every kernel works on v = srcs[r] + res[r].
- *   block_absmax_ef  block_absmax of v; the residuals are only read
- *   pack_block16_ef  stream_block16's F32 -> P16 of v at the agreed words; res[r][i] becomes what the
- *                    lane did not carry, 0 in a block whose word has bit 31
- *   block_fused_ef   block_fused with p16 != 0 of v, the residuals rewritten alike */
-int inccl_k_block_absmax_ef(const void *const *srcs, const float *const *res, int R, size_t n, uint32_t *words_dev,
-                            int flags, void *stream);
-int inccl_k_pack_block16_ef(const void *const *srcs, float *const *res, int R, void *dst, size_t n,
-                            const uint32_t *words_dev, size_t nb, size_t elem_base, int scale_R, void *stream);
-int inccl_k_block_fused_ef(const void *const *srcs, float *const *res, int R, void *dst, size_t n,
-                           uint32_t *words_out_dev, int flags, int scale_R, int out_shift, void *stream);
 void inccl_k_set_tuning(int grid_cap, int nt_loads);
 /* p2p engine kernels reading peer memory with system-coherent loads (inccl_peer.hip).
  * The pull-reduce, n % 4 == 0, by out_kind:

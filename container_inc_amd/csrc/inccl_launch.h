@@ -1,6 +1,6 @@
 // inccl_launch.h -- the host side of every kernel launch, once: pointer
 // alignment, the cached CU count, the grid arithmetic, the SrcPtrs fill and the
-// dispatch on the fan-in R.  Included by all eight .hip files.
+// dispatch on the fan-in R.  Included by all seven .hip files.
 #ifndef INCCL_LAUNCH_H
 #define INCCL_LAUNCH_H
 
@@ -43,11 +43,13 @@ inline int grid_of(int64_t items, int64_t per_group, int per_cu_cap)
     return grid_capped(items, per_group, (int64_t)num_cus() * per_cu_cap);
 }
 
-// s = the R pointers of srcs, none NULL; *vec stays true while all are 16-B aligned
-inline int fill_srcs(const void* const* srcs, int R, SrcPtrs* s, bool* vec)
+// s = the R pointers of srcs, none NULL; *vec stays true while all are 16-B
+// aligned (PTRS: SrcPtrs, or the ResPtrs of inccl_block.h for fp32 residuals)
+template <class T, class PTRS>
+inline int fill_srcs(T* const* srcs, int R, PTRS* s, bool* vec)
 {
     if (srcs == nullptr || R < 1 || R > kMaxR) return INCCL_ERR_ARG;
-    *s = SrcPtrs{};
+    *s = PTRS{};
     for (int r = 0; r < R; ++r) {
         if (srcs[r] == nullptr) return INCCL_ERR_ARG;
         s->p[r] = srcs[r];

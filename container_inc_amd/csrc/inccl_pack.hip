@@ -29,8 +29,18 @@
 //                          lane is then skipped
 // The one-pass world-1 form is k_stream_block_fused<.., P16 = true> of inccl_block.hip.
 //
-// Nontemporal loads, vector stores and plain C++.  Every lane of a wave reaches
-// k_pack_block's __shfl_xor: the loop around it is wave-uniform.
+// Error feedback (EF, inccl_block.h) is a compile-time switch of the two pack
+// kernels: the residuals are a parameter pack RES..., empty or one ResPtrs,
+// right after the sources (inccl_block.hip says why).  With EF they pack v = x + e:
+//   k_pack_block<R, B, ResPtrs>     e read by the same two rows, e' written by
+//                                   two dwordx4 stores per input;
+//                                   (12 R + 2) n + n / 64 bytes
+//   k_pack_block_elem<R, ResPtrs>   per word
+// The unpack kernels have no such form.
+//
+// Nontemporal loads, vector stores (nontemporal for the residual quads) and
+// plain C++.  Every lane of a wave reaches k_pack_block's __shfl_xor: the loop
+// around it is wave-uniform.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -39,8 +49,6 @@
 namespace {
 
 using namespace inccl_dev;
-
-__device__ __forceinline__ uint32_t pack2(uint32_t lo, uint32_t hi) { return hi * 65536u + lo; }
 
 __device__ __forceinline__ int32_t lane_lo(uint32_t s) { return (int32_t)(int16_t)(uint16_t)s; }
 __device__ __forceinline__ int32_t lane_hi(uint32_t s) { return (int32_t)(s - (uint32_t)lane_lo(s)) >> 16; }
@@ -55,11 +63,14 @@ __device__ __forceinline__ uint32_t deq1(int32_t lane, float inv) { return __flo
 // store covers two contiguous 512-B runs.  Quad q holds the bucket's elements
 // elem_base + 4 q .. + 3, inside one block since elem_base % 4 == 0.  The loop
 // is over whole waves (ntiles tiles of 128 quads): wave-uniform around the shuffles.
-template <int R, int BLOCK>
-__global__ __launch_bounds__(BLOCK) void k_pack_block(SrcPtrs src, void* __restrict__ dst, int64_t ntiles,
-                                                      const uint32_t* __restrict__ words, int64_t nb,
+// EF: each lane also writes back the two residual quads it read.
+template <int R, int BLOCK, class... RES>
+__global__ __launch_bounds__(BLOCK) void k_pack_block(SrcPtrs src, RES... res_arg, void* __restrict__ dst,
+                                                      int64_t ntiles, const uint32_t* __restrict__ words, int64_t nb,
                                                       int64_t elem_base, int scale_R, int L)
 {
+    constexpr bool EF = sizeof...(RES) != 0;
+    const Res<EF> res = res_of(res_arg...);
     constexpr int WAVES = BLOCK / 64;
     const int lane = threadIdx.x & 63;
     u32x4* __restrict__ out = reinterpret_cast<u32x4*>(dst);
@@ -68,25 +79,24 @@ __global__ __launch_bounds__(BLOCK) void k_pack_block(SrcPtrs src, void* __restr
         u32x4 a[R], b[R];
 #pragma unroll
         for (int r = 0; r < R; ++r) {
-            a[r] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(src.p[r]) + qa);
-            b[r] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(src.p[r]) + qb);
+            a[r] = ld_quad<EF>(src.p[r], res, r, qa);
+            b[r] = ld_quad<EF>(src.p[r], res, r, qb);
         }
-        const float sa = block_mul<true>(word_at(words, (elem_base + (qa << 2)) >> 8, nb), scale_R, 0).scale;
-        const float sb = block_mul<true>(word_at(words, (elem_base + (qb << 2)) >> 8, nb), scale_R, 0).scale;
-        uint32_t acc[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+        const uint32_t wa = word_at(words, (elem_base + (qa << 2)) >> 8, nb);
+        const auto ma = contrib_mul<EF>(block_mul<true>(wa, scale_R, 0), wa, scale_R);
+        const uint32_t wb = word_at(words, (elem_base + (qb << 2)) >> 8, nb);
+        const auto mb = contrib_mul<EF>(block_mul<true>(wb, scale_R, 0), wb, scale_R);
+        u32x4 sa = {0u, 0u, 0u, 0u}, sb = {0u, 0u, 0u, 0u};
 #pragma unroll
         for (int r = 0; r < R; ++r) {
-            acc[0] += quantb<true>(__uint_as_float(a[r].x), sa, L);
-            acc[1] += quantb<true>(__uint_as_float(a[r].y), sa, L);
-            acc[2] += quantb<true>(__uint_as_float(a[r].z), sa, L);
-            acc[3] += quantb<true>(__uint_as_float(a[r].w), sa, L);
-            acc[4] += quantb<true>(__uint_as_float(b[r].x), sb, L);
-            acc[5] += quantb<true>(__uint_as_float(b[r].y), sb, L);
-            acc[6] += quantb<true>(__uint_as_float(b[r].z), sb, L);
-            acc[7] += quantb<true>(__uint_as_float(b[r].w), sb, L);
+            u32x4 ea, eb;
+            contrib_quad<true, EF>(sa, a[r], ma, L, &ea);
+            contrib_quad<true, EF>(sb, b[r], mb, L, &eb);
+            st_quad<EF>(res, r, qa, ea);
+            st_quad<EF>(res, r, qb, eb);
         }
-        const uint32_t a0 = pack2(acc[0], acc[1]), a1 = pack2(acc[2], acc[3]);
-        const uint32_t b0 = pack2(acc[4], acc[5]), b1 = pack2(acc[6], acc[7]);
+        const uint32_t a0 = pack2(sa.x, sa.y), a1 = pack2(sa.z, sa.w);
+        const uint32_t b0 = pack2(sb.x, sb.y), b1 = pack2(sb.z, sb.w);
         const bool odd = lane & 1;
         const uint32_t r0 = (uint32_t)__shfl_xor((int)(odd ? a0 : b0), 1, 64);
         const uint32_t r1 = (uint32_t)__shfl_xor((int)(odd ? a1 : b1), 1, 64);
@@ -97,22 +107,30 @@ __global__ __launch_bounds__(BLOCK) void k_pack_block(SrcPtrs src, void* __restr
 
 // words [begin, m) of the call, m = ceil(n / 2); elem_base is even, so both
 // elements of a word are in one block
-template <int R>
-__global__ __launch_bounds__(kBlock) void k_pack_block_elem(SrcPtrs src, void* __restrict__ dst, int64_t begin,
-                                                            int64_t n, const uint32_t* __restrict__ words, int64_t nb,
+template <int R, class... RES>
+__global__ __launch_bounds__(kBlock) void k_pack_block_elem(SrcPtrs src, RES... res_arg, void* __restrict__ dst,
+                                                            int64_t begin, int64_t n,
+                                                            const uint32_t* __restrict__ words, int64_t nb,
                                                             int64_t elem_base, int scale_R, int L)
 {
+    constexpr bool EF = sizeof...(RES) != 0;
+    const Res<EF> res = res_of(res_arg...);
     uint32_t* __restrict__ out = reinterpret_cast<uint32_t*>(dst);
     const int64_t m = (n + 1) >> 1;
     for (int64_t j = begin + (int64_t)blockIdx.x * kBlock + threadIdx.x; j < m; j += (int64_t)gridDim.x * kBlock) {
-        const float scale = block_mul<true>(word_at(words, (elem_base + 2 * j) >> 8, nb), scale_R, 0).scale;
+        const uint32_t w = word_at(words, (elem_base + 2 * j) >> 8, nb);
+        const auto mul = contrib_mul<EF>(block_mul<true>(w, scale_R, 0), w, scale_R);
         const bool pair = 2 * j + 1 < n;
         uint32_t lo = 0, hi = 0;
 #pragma unroll
         for (int r = 0; r < R; ++r) {
-            const float* __restrict__ x = reinterpret_cast<const float*>(src.p[r]);
-            lo += quantb<true>(x[2 * j], scale, L);
-            if (pair) hi += quantb<true>(x[2 * j + 1], scale, L);
+            uint32_t e;
+            lo += contrib<true, EF>(ld1<EF>(src.p[r], res, r, 2 * j), mul, L, &e);
+            st1<EF>(res, r, 2 * j, e);
+            if (pair) {
+                hi += contrib<true, EF>(ld1<EF>(src.p[r], res, r, 2 * j + 1), mul, L, &e);
+                st1<EF>(res, r, 2 * j + 1, e);
+            }
         }
         out[j] = pack2(lo, hi);
     }
@@ -159,9 +177,10 @@ __global__ __launch_bounds__(kBlock) void k_unpack_block_elem(SrcPtrs src, void*
     }
 }
 
+// e: the residuals (error feedback) or NULL
 template <int R>
-void launch_pack(const SrcPtrs& s, void* dst, int64_t n, const uint32_t* words, int64_t nb, int64_t elem_base,
-                 int scale_R, bool vec, hipStream_t st)
+void launch_pack(const SrcPtrs& s, const ResPtrs* e, void* dst, int64_t n, const uint32_t* words, int64_t nb,
+                 int64_t elem_base, int scale_R, bool vec, hipStream_t st)
 {
     constexpr int B = 512;
     const int L = inccl_p16_clamp(scale_R);
@@ -169,14 +188,24 @@ void launch_pack(const SrcPtrs& s, void* dst, int64_t n, const uint32_t* words, 
     int64_t done = 0;   // words
     if (vec && (elem_base & 3) == 0) {
         const int64_t ntiles = n >> 9;   // whole waves of 512 elements
-        if (ntiles > 0)
-            hipLaunchKernelGGL((k_pack_block<R, B>), dim3(grid_of(ntiles, B / 64, 8)), dim3(B), 0, st, s, dst, ntiles,
-                               words, nb, elem_base, scale_R, L);
+        const dim3 grid(grid_of(ntiles, B / 64, 8));
+        if (ntiles > 0 && e)
+            hipLaunchKernelGGL((k_pack_block<R, B, ResPtrs>), grid, dim3(B), 0, st, s, *e, dst, ntiles, words, nb, elem_base,
+                               scale_R, L);
+        else if (ntiles > 0)
+            hipLaunchKernelGGL((k_pack_block<R, B>), grid, dim3(B), 0, st, s, dst, ntiles, words, nb, elem_base, scale_R,
+                               L);
         done = ntiles << 8;
     }
-    if (done < m)
-        hipLaunchKernelGGL((k_pack_block_elem<R>), dim3(grid_of(m - done, kBlock, 8)), dim3(kBlock), 0, st, s, dst, done,
-                           n, words, nb, elem_base, scale_R, L);
+    if (done < m) {
+        const dim3 grid(grid_of(m - done, kBlock, 8));
+        if (e)
+            hipLaunchKernelGGL((k_pack_block_elem<R, ResPtrs>), grid, dim3(kBlock), 0, st, s, *e, dst, done, n, words, nb,
+                               elem_base, scale_R, L);
+        else
+            hipLaunchKernelGGL((k_pack_block_elem<R>), grid, dim3(kBlock), 0, st, s, dst, done, n, words, nb, elem_base,
+                               scale_R, L);
+    }
 }
 
 template <int R>
@@ -201,22 +230,26 @@ void launch_unpack(const SrcPtrs& s, void* dst, int64_t n, const uint32_t* words
 
 extern "C" {
 
-int inccl_k_stream_block16(int in_kind, int out_kind, const void* const* srcs, int R, void* dst, size_t n,
-                           const uint32_t* words_dev, size_t nb, size_t elem_base, int scale_R, int out_shift,
-                           void* stream)
+int inccl_k_stream_block16(int in_kind, int out_kind, const void* const* srcs, float* const* res, int R, void* dst,
+                           size_t n, const uint32_t* words_dev, size_t nb, size_t elem_base, int scale_R,
+                           int out_shift, void* stream)
 {
     SrcPtrs s;
+    ResPtrs e;
     bool vec = aligned16(dst);
     const bool pack = in_kind == F32 && out_kind == P16, unpack = in_kind == P16 && out_kind == F32;
-    if (fill_srcs(srcs, R, &s, &vec) || (!pack && !unpack) || (dst == nullptr && n > 0) || out_shift < 0 ||
-        out_shift > 8 || ((words_dev == nullptr || nb == 0) && n > 0) || (pack && (elem_base & 1)))
+    if (fill_srcs(srcs, R, &s, &vec) || (res != nullptr && (!pack || fill_srcs(res, R, &e, &vec))) ||
+        (!pack && !unpack) || (dst == nullptr && n > 0) || out_shift < 0 || out_shift > 8 ||
+        ((words_dev == nullptr || nb == 0) && n > 0) || (pack && (elem_base & 1)))
         return INCCL_ERR_ARG;
     if (scale_R <= 0) scale_R = R;
     if (scale_R > INCCL_P16_LANE_MAX) return INCCL_ERR_ARG;
     if (n == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
 #define INCCL_CALL(RR)                                                                                             \
-    if (pack) launch_pack<RR>(s, dst, (int64_t)n, words_dev, (int64_t)nb, (int64_t)elem_base, scale_R, vec, st);   \
+    if (pack)                                                                                                      \
+        launch_pack<RR>(s, res ? &e : nullptr, dst, (int64_t)n, words_dev, (int64_t)nb, (int64_t)elem_base, scale_R, \
+                        vec, st);                                                                                  \
     else launch_unpack<RR>(s, dst, (int64_t)n, words_dev, (int64_t)nb, (int64_t)elem_base, scale_R, out_shift, vec, st)
     INCCL_R_SWITCH(R, INCCL_CALL)
 #undef INCCL_CALL

@@ -141,6 +141,32 @@ def test_pack_at_an_offset(gpu, elem_base, copy):
             _same(_np(f), want)
 
 
+@pytest.mark.parametrize("elem_base", [0, 4, 2])
+def test_pack_with_zero_residuals_is_the_plain_pack(gpu, elem_base):
+    """No residuals and zero residuals are one kernel body: at R = 3 and
+    n = 2341 (elem_base 0 and 4: four tiles of the vector kernel and a tail;
+    2: per word throughout), pack_block16_ef with zero residuals returns exactly
+    the words of stream_op_block's F32 -> P16 on the same buckets and words, and
+    leaves the reference's residuals.  The call's elements are elements
+    elem_base .. of a bucket that is zero before them."""
+    from container_inc_amd import inccl
+    orc = _orc()
+    R, n = 3, 2341
+    bufs, _ = _case(R, n)
+    words = block_ref.block_words(orc, [np.concatenate([np.zeros(elem_base, np.float32), x]) for x in bufs])
+    ks = block16_ref.block_scales16(orc, words, R)
+    wt = _t(words.view(np.int32), gpu)
+    ts = [_t(x, gpu) for x in bufs]
+    rs = [_t(np.zeros(n, np.float32), gpu) for _ in bufs]
+    plain = _np(inccl.stream_op_block(inccl.KIND_F32, inccl.KIND_P16, ts, wt, elem_base=elem_base, scale_R=R))
+    got = _np(inccl.pack_block16_ef(ts, rs, wt, elem_base=elem_base, scale_R=R))
+    np.testing.assert_array_equal(got, plain)
+    np.testing.assert_array_equal(got, block16_ref.pack_quant_sum(orc, bufs, ks, R, elem_base))
+    for v, r in zip(ef.add(bufs, ef.zeros_like(bufs)), rs):
+        _same(_np(r), ef.residual(orc, v, words, ks, R, elem_base)[0])
+    assert any(_np(r).any() for r in rs)
+
+
 def test_pack_refuses_an_odd_elem_base(gpu):
     import torch
     from container_inc_amd import inccl

@@ -2,12 +2,12 @@
 """Error feedback for packed 16-bit lanes (inccl_*_ef) against the same kernels
 without it, on one GPU, R = 2 x 256 MiB fp32 buckets (and as many residuals):
 
-  quant   quant16_ef   inccl_pack_f32_block16_ef    k_pack_block_ef          (12 R + 2) n + n / 64 bytes
-          quant16      F32 -> P16                   k_pack_block             (4 R + 2) n + n / 64
-  absmax  absmax_ef    inccl_block_absmax_f32_ef    k_block_absmax_ef        8 R n + n / 64
-          absmax       inccl_block_absmax_f32       k_block_absmax           4 R n + n / 64
-  fused   fused16_ef   inccl_reduce_f32_block16_ef  k_stream_block_fused_ef  (12 R + 4) n
-          fused16      inccl_reduce_f32_block16     k_stream_block_fused     (4 R + 4) n
+  quant   quant16_ef   inccl_pack_f32_block16_ef    k_pack_block<.., ResPtrs>          (12 R + 2) n + n / 64 bytes
+          quant16      F32 -> P16                   k_pack_block                       (4 R + 2) n + n / 64
+  absmax  absmax_ef    inccl_block_absmax_f32_ef    k_block_absmax<.., ResPtrs>        8 R n + n / 64
+          absmax       inccl_block_absmax_f32       k_block_absmax                     4 R n + n / 64
+  fused   fused16_ef   inccl_reduce_f32_block16_ef  k_stream_block_fused<.., ResPtrs>  (12 R + 4) n
+          fused16      inccl_reduce_f32_block16     k_stream_block_fused               (4 R + 4) n
 
 The discipline is tools/pack_bench.py's, whose timing it uses: each leg warmed
 up, the two legs of a group timed in alternating rounds, a leg's figure the
