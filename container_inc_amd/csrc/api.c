@@ -53,28 +53,6 @@ int inccl_ensure_dev(void **p, size_t *cur, size_t need)
     return 0;
 }
 
-/* Device memory that peers map over HIP IPC and that a running kernel polls or
- * reads after a flag (the ll and mesh engines).  Default "uncached"
- * (hipDeviceMallocUncached): every access bypasses the L2, so a remote GPU's
- * xGMI store into this HBM cannot hide behind a line this GPU's L2 cached
- * before it.  Coarse-grained hipMalloc memory is only guaranteed coherent with
- * other agents at kernel boundaries.  $INCCL_IPC_MEM = uncached | finegrained |
- * coarse selects the kind (same on every rank). */
-unsigned inccl_ipc_mem_flags(void)
-{
-    const char *e = getenv("INCCL_IPC_MEM");
-    if (e && strcmp(e, "coarse") == 0) return hipDeviceMallocDefault;
-    if (e && strcmp(e, "finegrained") == 0) return hipDeviceMallocFinegrained;
-    return hipDeviceMallocUncached;
-}
-
-hipError_t inccl_ipc_malloc(void **p, size_t bytes)
-{
-    const unsigned f = inccl_ipc_mem_flags();
-    if (f == hipDeviceMallocDefault) return hipMalloc(p, bytes);
-    return hipExtMallocWithFlags(p, bytes, f);
-}
-
 int inccl_mem_kind(const void *p)
 {
     if (!p) return inccl_set_error(INCCL_ERR_ARG, "mem_kind: NULL pointer");
@@ -730,14 +708,8 @@ static int comm_init(struct inccl_communicator *c, uint32_t size)
                  * ranks sharing one GPU), every rank switches to the IPC p2p
                  * engine alike; the rccl engine can still be selected later and
                  * then reports its own error */
-                int32_t mine = rc ? 1 : 0;
-                int32_t *all = (int32_t *)calloc((size_t)g->world_size, sizeof(int32_t));
-                if (!all) return inccl_set_error(INCCL_ERR_NOMEM, "communicator: out of memory");
-                int rc2 = inccl_boot_allgather(g, &mine, all, sizeof(int32_t));
                 int failed = -1;
-                for (int j = 0; !rc2 && j < g->world_size; ++j)
-                    if (all[j] && failed < 0) failed = j;
-                free(all);
+                int rc2 = inccl_boot_agree(g, rc != 0, &failed);
                 if (rc2) return rc2;
                 if (failed >= 0) {
                     fprintf(stderr, "inccl: RCCL communicator unavailable on rank %d%s%s; using the p2p engine\n",
@@ -763,7 +735,7 @@ int inccl_communicator_destroy(struct inccl_communicator *comm)
     if (!comm) return 0;
     if (comm->group->device >= 0) hipSetDevice(comm->group->device);
     if (comm->stream) hipStreamSynchronize(comm->stream);
-    if (comm->p2p_part || comm->ll_buf || comm->mesh_buf) {   /* peers may still be reading our IPC buffers */
+    if (comm->p2p_ipc.n || comm->ll_ipc.n || comm->mesh_ipc.n) {   /* peers may still be reading our IPC buffers */
         hipDeviceSynchronize();   /* our queued reads of theirs have drained ... */
         inccl_boot_barrier(comm->group);   /* ... and so have everyone else's */
         inccl_p2p_release(comm);
@@ -880,9 +852,9 @@ int inccl_comm_ipc_mem_kind(struct inccl_communicator *comm, const char *engine)
 {
     if (!comm || !engine) return inccl_set_error(INCCL_ERR_ARG, "bad ipc_mem_kind args");
     const void *p = NULL;
-    if (strcmp(engine, "ll") == 0) p = comm->ll_buf;
-    else if (strcmp(engine, "mesh") == 0 || strcmp(engine, "meshw") == 0) p = comm->mesh_reg[1];   /* the inbox */
-    else if (strcmp(engine, "p2p") == 0) p = comm->p2p_part;
+    if (strcmp(engine, "ll") == 0) p = comm->ll_ipc.own[0];
+    else if (strcmp(engine, "mesh") == 0 || strcmp(engine, "meshw") == 0) p = comm->mesh_ipc.own[1];   /* the inbox */
+    else if (strcmp(engine, "p2p") == 0) p = comm->p2p_ipc.own[0];
     else return inccl_set_error(INCCL_ERR_ARG, "ipc_mem_kind: unknown engine '%s' (ll | mesh | p2p)", engine);
     if (!p) return inccl_set_error(INCCL_ERR_STATE, "ipc_mem_kind: engine '%s' has no IPC buffer yet", engine);
     if (comm->group->device >= 0) INCCL_HIP(hipSetDevice(comm->group->device));

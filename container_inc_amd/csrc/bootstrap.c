@@ -218,6 +218,18 @@ int inccl_boot_allgather(struct inccl_group *g, const void *mine, void *all, siz
     return 0;
 }
 
+int inccl_boot_agree(struct inccl_group *g, int local_failed, int *first_failed_rank)
+{
+    *first_failed_rank = -1;
+    int32_t mine = local_failed ? 1 : 0, *all = (int32_t *)calloc((size_t)g->world_size, sizeof(int32_t));
+    if (!all) return inccl_set_error(INCCL_ERR_NOMEM, "bootstrap: out of memory");
+    int rc = inccl_boot_allgather(g, &mine, all, sizeof(int32_t));
+    for (int j = g->world_size - 1; !rc && j >= 0; --j)
+        if (all[j]) *first_failed_rank = j;
+    free(all);
+    return rc;
+}
+
 int inccl_boot_barrier(struct inccl_group *g)
 {
     if (g->world_size == 1) return 0;

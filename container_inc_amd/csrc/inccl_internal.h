@@ -53,6 +53,17 @@ struct inccl_group {
     int comm_seq;   /* communicators created so far (names the hub slot) */
 };
 
+/* One engine's device buffers shared with every peer over HIP IPC (ipc.c).
+ * polled: a running kernel polls the memory or reads it after a flag
+ * (inccl_ipc_malloc, $INCCL_IPC_MEM), else plain hipMalloc; zero_bytes: the
+ * leading bytes zeroed before any peer maps the region.  n == 0: empty. */
+struct inccl_ipc_region { size_t bytes; int polled; size_t zero_bytes; };
+struct inccl_ipc_set {
+    int n;                                                   /* regions, <= INCCL_MESH_REGIONS */
+    char *own[INCCL_MESH_REGIONS];
+    char *peer[INCCL_MESH_REGIONS][INCCL_MAX_LOCAL_INPUTS];  /* rank j's region r ([r][me] == own[r]) */
+};
+
 struct inccl_communicator {
     struct inccl_group *group;
     uint32_t payload_buf_size;   /* 2*size bytes, api.c:164 */
@@ -82,14 +93,11 @@ struct inccl_communicator {
     int nonfinite;               /* INCCL_NONFINITE_* (inccl_comm_set_nonfinite) */
     int wire;                    /* INCCL_WIRE_* (inccl_comm_set_wire): what INCCL_SCALE_BLOCK calls exchange */
     size_t p2p_cap;              /* elements per buffer */
-    int32_t *p2p_part;           /* this rank's quantised partial sums (W * shard) */
-    float *p2p_res;              /* this rank's dequantised shard lives at rank * shard */
-    int32_t *p2p_peer_part[INCCL_MAX_LOCAL_INPUTS];
-    float *p2p_peer_res[INCCL_MAX_LOCAL_INPUTS];
+    struct inccl_ipc_set p2p_ipc;   /* [0] part: this rank's int32 partial sums (W * shard); [1] res: its
+                                     * dequantised shard lives at rank * shard */
     /* ll engine (small buckets, one kernel per call): one IPC buffer per rank =
      * signal array + call counter + two parity data slots */
-    char *ll_buf;
-    char *ll_peer[INCCL_MAX_LOCAL_INPUTS];
+    struct inccl_ipc_set ll_ipc;
     size_t ll_cap;               /* elements per data slot */
     uint32_t *ll_err_host;       /* host-mapped: set by a kernel whose peers timed out */
     uint32_t *ll_err_dev;
@@ -106,11 +114,10 @@ struct inccl_communicator {
      * environments differ still take the same route on every call */
     size_t rccl_ar_bytes;        /* rccl engine: int32 partials up to this size take one
                                     ncclAllReduce instead of reduce-scatter + all-gather */
-    /* mesh engine (large buckets, one persistent kernel per call): one IPC buffer
-     * per rank = signal array + counters + inbox (W partial shards) + result shard */
-    char *mesh_buf;                                        /* = mesh_reg[0]: signals + counters */
-    char *mesh_reg[INCCL_MESH_REGIONS];                    /* sig, inbox, result shard, result inbox */
-    char *mesh_peer[INCCL_MESH_REGIONS][INCCL_MAX_LOCAL_INPUTS];   /* rank j's regions ([r][me] = own) */
+    /* mesh engine (large buckets, one persistent kernel per call): four IPC
+     * regions per rank = signals + counters, inbox (W partial shards), result
+     * shard, result inbox */
+    struct inccl_ipc_set mesh_ipc;
     size_t mesh_cap;             /* elements per inbox slot / result shard */
     int mesh_grid;               /* this rank's workgroups per call */
     uint32_t *mesh_err_host;     /* host-mapped: set by a kernel whose peers timed out */
@@ -226,6 +233,8 @@ int inccl_boot_worker(struct inccl_group *g);
 int inccl_boot_bcast(struct inccl_group *g, void *buf, size_t bytes);   /* from rank 0 */
 int inccl_boot_barrier(struct inccl_group *g);
 int inccl_boot_allgather(struct inccl_group *g, const void *mine, void *all, size_t bytes);
+/* agree on an outcome: *first_failed_rank = the lowest rank that passed local_failed != 0, or -1 */
+int inccl_boot_agree(struct inccl_group *g, int local_failed, int *first_failed_rank);
 int inccl_boot_shm_init(struct inccl_group *g);   /* collective; falls back silently */
 int inccl_group_barrier(struct inccl_group *g);   /* shm barrier if set up, else TCP */
 int inccl_group_allreduce_max_u32(struct inccl_group *g, uint32_t *v);   /* through shm if set up, else TCP */
@@ -252,9 +261,19 @@ int inccl_ensure_dev(void **p, size_t *cur, size_t need);
 /* before a call first uses the communicator's shared workspaces (d_q32, d_f32,
  * d_words): orders it after the last call that used them on another stream */
 int inccl_ws_claim(struct inccl_communicator *c, hipStream_t st);
-/* IPC-shared device memory polled by running kernels (ll, mesh): $INCCL_IPC_MEM */
+/* ipc.c.  IPC-shared device memory polled by running kernels (ll, mesh): $INCCL_IPC_MEM */
 unsigned inccl_ipc_mem_flags(void);
 hipError_t inccl_ipc_malloc(void **p, size_t bytes);
+/* collective: every rank calls it with the same regions.  Replaces *s by a new
+ * set that every peer has mapped (make before break); on any failure *s is left
+ * empty and every connected rank returns an error.  local_rc: a failure the
+ * caller already has, carried to the agreement (the rank still takes every
+ * collective step) */
+int inccl_ipc_set_replace(struct inccl_group *g, struct inccl_ipc_set *s, const struct inccl_ipc_region *regions,
+                          int n, int local_rc, const char *who);
+void inccl_ipc_set_release(struct inccl_group *g, struct inccl_ipc_set *s);   /* not collective; no-op when empty */
+int inccl_err_words_create(uint32_t **host, uint32_t **dev, int words);
+void inccl_err_words_destroy(uint32_t **host, uint32_t **dev);
 int inccl_mem_kind(const void *p);   /* hipPointerAttribute_t.allocationFlags */
 
 /* copypool.c */

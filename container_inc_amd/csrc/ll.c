@@ -27,68 +27,26 @@
 
 void inccl_ll_release(struct inccl_communicator *c)
 {
-    const int W = c->group->world_size, me = c->group->rank;
-    if (!c->ll_buf) return;
-    hipDeviceSynchronize();
-    for (int j = 0; j < W && j < INCCL_MAX_LOCAL_INPUTS; ++j) {
-        if (j != me && c->ll_peer[j]) hipIpcCloseMemHandle(c->ll_peer[j]);
-        c->ll_peer[j] = NULL;
-    }
-    hipFree(c->ll_buf);
-    c->ll_buf = NULL;
-    if (c->ll_err_host) hipHostFree(c->ll_err_host);
-    c->ll_err_host = NULL;
-    c->ll_err_dev = NULL;
+    inccl_ipc_set_release(c->group, &c->ll_ipc);
+    inccl_err_words_destroy(&c->ll_err_host, &c->ll_err_dev);
     c->ll_cap = 0;
 }
 
 static int ll_ensure(struct inccl_communicator *c)
 {
     struct inccl_group *g = c->group;
-    const int W = g->world_size, me = g->rank;
-    if (c->ll_buf) return 0;
-    if (W > INCCL_MAX_LOCAL_INPUTS)
+    if (c->ll_ipc.own[0]) return 0;
+    if (g->world_size > INCCL_MAX_LOCAL_INPUTS)
         return inccl_set_error(INCCL_ERR_ARG, "ll engine supports up to %d GPUs", INCCL_MAX_LOCAL_INPUTS);
-    int rc = 0;
     const size_t cap = (c->ll_max_bytes / 4 + 1023) & ~(size_t)1023;
-    hipIpcMemHandle_t mine, all[INCCL_MAX_LOCAL_INPUTS];
-    memset(&mine, 0, sizeof(mine));
-    /* local failures are carried to the collective outcome check below */
-    hipError_t e = inccl_ipc_malloc((void **)&c->ll_buf, LL_SIG_BYTES + 2 * cap * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMemset(c->ll_buf, 0, LL_SIG_BYTES);   /* synchronous: zero before any peer maps it */
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipIpcGetMemHandle(&mine, c->ll_buf);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&c->ll_err_host, sizeof(uint32_t), hipHostMallocMapped);
-    if (e == hipSuccess) {
-        *(volatile uint32_t *)c->ll_err_host = 0;
-        e = hipHostGetDevicePointer((void **)&c->ll_err_dev, c->ll_err_host, 0);
-    }
-    if (e != hipSuccess) rc = inccl_hip_check(e, "ll: buffer setup");
-    int rc_x = inccl_boot_allgather(g, &mine, all, sizeof(hipIpcMemHandle_t));
-    if (rc_x) {
+    /* polled by the running kernel; signals and counters start at zero */
+    const struct inccl_ipc_region region = {LL_SIG_BYTES + 2 * cap * sizeof(uint32_t), 1, LL_SIG_BYTES};
+    int rc = inccl_err_words_create(&c->ll_err_host, &c->ll_err_dev, 1);
+    rc = inccl_ipc_set_replace(g, &c->ll_ipc, &region, 1, rc, "ll");
+    if (rc) {
         inccl_ll_release(c);   /* back to a clean state: the next call starts over */
-        return rc_x;
+        return rc;
     }
-    for (int j = 0; rc == 0 && j < W; ++j) {
-        if (j == me) {
-            c->ll_peer[j] = c->ll_buf;
-            continue;
-        }
-        void *p = NULL;
-        e = hipIpcOpenMemHandle(&p, all[j], hipIpcMemLazyEnablePeerAccess);
-        if (e != hipSuccess) rc = inccl_hip_check(e, "ll: hipIpcOpenMemHandle");
-        c->ll_peer[j] = (char *)p;
-    }
-    /* agree on the outcome, so that every rank falls back alike */
-    int32_t mine_rc = rc ? 1 : 0, all_rc[INCCL_MAX_LOCAL_INPUTS];
-    int rc2 = inccl_boot_allgather(g, &mine_rc, all_rc, sizeof(int32_t));
-    if (rc2) return rc2;
-    for (int j = 0; j < W; ++j)
-        if (all_rc[j]) {
-            if (!rc) rc = inccl_set_error(INCCL_ERR_HIP, "ll: rank %d could not map the peer buffers", j);
-            inccl_ll_release(c);
-            return rc;
-        }
     c->ll_cap = cap;
     c->ll_last_stream = NULL;
     if (c->ll_timeout_ticks == 0) c->ll_timeout_ticks = inccl_wait_ticks(g);
@@ -111,7 +69,7 @@ int inccl_ll_piece(struct inccl_communicator *c, const float *const *srcs, int R
                    const struct inccl_scale *sc, size_t rs_lo, size_t rs_n, hipStream_t st)
 {
     const int W = c->group->world_size, me = c->group->rank;
-    if (!c->ll_buf) {   /* the collective setup cannot run inside a graph capture */
+    if (!c->ll_ipc.own[0]) {   /* the collective setup cannot run inside a graph capture */
         hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
         INCCL_HIP(hipStreamIsCapturing(st, &cap));
         if (cap != hipStreamCaptureStatusNone)
@@ -128,14 +86,14 @@ int inccl_ll_piece(struct inccl_communicator *c, const float *const *srcs, int R
     l.R = R;
     l.dst = dst;
     l.n = n;
-    l.own_data = (uint32_t *)(c->ll_buf + LL_SIG_BYTES);
+    l.own_data = (uint32_t *)(c->ll_ipc.own[0] + LL_SIG_BYTES);
     l.slot_elems = c->ll_cap;
     for (int j = 0; j < W; ++j) {
-        l.peer_data[j] = (const uint32_t *)(c->ll_peer[j] + LL_SIG_BYTES);
-        l.peer_sig[j] = (uint32_t *)c->ll_peer[j];
+        l.peer_data[j] = (const uint32_t *)(c->ll_ipc.peer[0][j] + LL_SIG_BYTES);
+        l.peer_sig[j] = (uint32_t *)c->ll_ipc.peer[0][j];
     }
-    l.own_sig = (const uint32_t *)c->ll_buf;
-    l.ctr = (uint32_t *)(c->ll_buf + LL_CTR_OFFSET);
+    l.own_sig = (const uint32_t *)c->ll_ipc.own[0];
+    l.ctr = (uint32_t *)(c->ll_ipc.own[0] + LL_CTR_OFFSET);
     l.err = c->ll_err_dev;
     l.W = W;
     l.me = me;

@@ -33,7 +33,7 @@
 #define MESH_CTR_OFFSET MESH_SIG_BYTES
 #define MESH_DATA_OFFSET (MESH_SIG_BYTES + (size_t)65536)
 
-/* $INCCL_TRACE: one timestamped line per setup step (debugging aid) */
+/* $INCCL_TRACE: one timestamped line per launch (debugging aid) */
 #define MTRACE(...)                                                                      \
     do {                                                                                 \
         if (getenv("INCCL_TRACE")) {                                                     \
@@ -47,27 +47,13 @@
     } while (0)
 
 typedef struct {
-    hipIpcMemHandle_t h[INCCL_MESH_REGIONS];
-    int pci_domain, pci_bus, pci_dev;   /* ranks sharing a GPU split its workgroup slots */
-} mesh_peer_info;
+    int32_t ok, pci_domain, pci_bus, pci_dev;   /* ranks sharing a GPU split its workgroup slots */
+} mesh_where;
 
 void inccl_mesh_release(struct inccl_communicator *c)
 {
-    const int W = c->group->world_size, me = c->group->rank;
-    if (!c->mesh_buf && !c->mesh_reg[1] && !c->mesh_reg[2] && !c->mesh_reg[3]) return;
-    hipDeviceSynchronize();
-    for (int r = 0; r < INCCL_MESH_REGIONS; ++r) {
-        for (int j = 0; j < W && j < INCCL_MAX_LOCAL_INPUTS; ++j) {
-            if (j != me && c->mesh_peer[r][j]) hipIpcCloseMemHandle(c->mesh_peer[r][j]);
-            c->mesh_peer[r][j] = NULL;
-        }
-        if (c->mesh_reg[r]) hipFree(c->mesh_reg[r]);
-        c->mesh_reg[r] = NULL;
-    }
-    c->mesh_buf = NULL;
-    if (c->mesh_err_host) hipHostFree(c->mesh_err_host);
-    c->mesh_err_host = NULL;
-    c->mesh_err_dev = NULL;
+    inccl_ipc_set_release(c->group, &c->mesh_ipc);
+    inccl_err_words_destroy(&c->mesh_err_host, &c->mesh_err_dev);
     c->mesh_cap = 0;
 }
 
@@ -85,8 +71,8 @@ static size_t mesh_region_bytes(int r, int W, size_t cap)
 static int mesh_ensure(struct inccl_communicator *c, size_t shard)
 {
     struct inccl_group *g = c->group;
-    const int W = g->world_size, me = g->rank;
-    if (c->mesh_buf && c->mesh_cap >= shard) return 0;
+    const int W = g->world_size;
+    if (c->mesh_ipc.own[0] && c->mesh_cap >= shard) return 0;
     if (W > INCCL_MAX_LOCAL_INPUTS)
         return inccl_set_error(INCCL_ERR_ARG, "mesh engine supports up to %d GPUs", INCCL_MAX_LOCAL_INPUTS);
     const size_t cap = (shard + ((size_t)1 << 19) - 1) & ~(((size_t)1 << 19) - 1);   /* 2 MiB granules */
@@ -95,65 +81,24 @@ static int mesh_ensure(struct inccl_communicator *c, size_t shard)
         return inccl_set_error(INCCL_ERR_ARG, "mesh: a %zu-element shard needs a %zu-byte inbox; this group's IPC "
                                "buffers stay below %zu bytes (under PyTorch's bundled HSA runtime, importing a larger "
                                "one hangs; runtime.c)", shard, mesh_region_bytes(1, W, cap), g->ipc_max_bytes);
-    /* make before break (as p2p_ensure): the old buffers stay alive, and mapped
-     * by the peers, until every rank has mapped the new ones */
-    struct inccl_communicator old = *c;
-    if (c->mesh_buf) {   /* everyone's queued accesses to the old buffers drain first */
-        MTRACE("mesh regrow %zu -> %zu: device sync", c->mesh_cap, shard);
-        INCCL_HIP(hipDeviceSynchronize());
-        int rc = inccl_boot_barrier(g);
-        if (rc) return rc;
-        c->mesh_buf = NULL;
-        c->mesh_err_host = NULL;
-        c->mesh_err_dev = NULL;
-        c->mesh_cap = 0;
-        memset(c->mesh_reg, 0, sizeof(c->mesh_reg));
-        memset(c->mesh_peer, 0, sizeof(c->mesh_peer));
-    }
     const int dev = g->device >= 0 ? g->device : 0;
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-    mesh_peer_info mine, *all = (mesh_peer_info *)calloc((size_t)W, sizeof(mesh_peer_info));
-    if (!all) {
-        inccl_mesh_release(&old);
-        return inccl_set_error(INCCL_ERR_NOMEM, "mesh: out of memory");
-    }
+    /* where everyone is: ranks sharing a GPU size their grids together.  Every
+     * rank sees the same gathered rows, so a bad one makes all of them fail alike */
+    mesh_where mine, all[INCCL_MAX_LOCAL_INPUTS];
     memset(&mine, 0, sizeof(mine));
-    int rc = 0;
-    /* local failures are carried to the collective outcome check below.  Four
-     * separate allocations, so that no single IPC export reaches 2 GiB for
-     * buckets up to ~2 GiB at any W */
-    hipError_t e = hipSuccess;
-    for (int r = 0; r < INCCL_MESH_REGIONS && e == hipSuccess; ++r) {
-        e = inccl_ipc_malloc((void **)&c->mesh_reg[r], mesh_region_bytes(r, W, cap));
-        if (e == hipSuccess) e = hipIpcGetMemHandle(&mine.h[r], c->mesh_reg[r]);
-    }
-    c->mesh_buf = c->mesh_reg[0];
-    if (e == hipSuccess) e = hipMemset(c->mesh_buf, 0, MESH_DATA_OFFSET);   /* flags + counters */
-    if (e == hipSuccess) e = hipDeviceSynchronize();   /* zeroed before any peer maps it */
-    if (e == hipSuccess) e = hipHostMalloc((void **)&c->mesh_err_host, 32 * sizeof(uint32_t), hipHostMallocMapped);
-    if (e == hipSuccess) {
-        for (int i = 0; i < 32; ++i) ((volatile uint32_t *)c->mesh_err_host)[i] = 0;
-        e = hipHostGetDevicePointer((void **)&c->mesh_err_dev, c->mesh_err_host, 0);
-    }
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&mine.pci_domain, hipDeviceAttributePciDomainID, dev);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&mine.pci_bus, hipDeviceAttributePciBusId, dev);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&mine.pci_dev, hipDeviceAttributePciDeviceId, dev);
-    if (e != hipSuccess) rc = inccl_hip_check(e, "mesh: buffer setup");
-    MTRACE("mesh alloc 4 regions, inbox %zu B (%s): allgather", mesh_region_bytes(1, W, cap),
-           e == hipSuccess ? "ok" : hipGetErrorString(e));
-    /* where everyone is: ranks sharing a GPU size their grids together */
-    int rc_x = inccl_boot_allgather(g, &mine, all, sizeof(mesh_peer_info));
-    if (rc_x) {
-        free(all);
-        inccl_mesh_release(c);   /* back to a clean state: the next call starts over */
-        inccl_mesh_release(&old);
-        return rc_x;
-    }
+    mine.ok = hipDeviceGetAttribute(&mine.pci_domain, hipDeviceAttributePciDomainID, dev) == hipSuccess &&
+              hipDeviceGetAttribute(&mine.pci_bus, hipDeviceAttributePciBusId, dev) == hipSuccess &&
+              hipDeviceGetAttribute(&mine.pci_dev, hipDeviceAttributePciDeviceId, dev) == hipSuccess;
+    int rc = inccl_boot_allgather(g, &mine, all, sizeof(mesh_where));
+    if (rc) return rc;
     int sharing = 0;
-    for (int j = 0; j < W; ++j)
+    for (int j = 0; j < W; ++j) {
+        if (!all[j].ok) return inccl_set_error(INCCL_ERR_HIP, "mesh: rank %d could not read its GPU's PCI ids", j);
         sharing += all[j].pci_domain == mine.pci_domain && all[j].pci_bus == mine.pci_bus &&
                    all[j].pci_dev == mine.pci_dev;
+    }
     /* two workgroups per CU; ranks sharing one GPU split those slots, so that
      * their grids co-reside (every k_mesh<R> fits two 256-lane workgroups per CU;
      * the schedule's progress argument needs each rank to keep one running) */
@@ -161,41 +106,18 @@ static int mesh_ensure(struct inccl_communicator *c, size_t shard)
     int grid = ge ? atoi(ge) : 0;
     if (grid <= 0) grid = 2 * cus / (sharing > 0 ? sharing : 1);
     if (grid < 4) grid = 4;
-    for (int j = 0; j < W; ++j)
-        for (int r = 0; r < INCCL_MESH_REGIONS; ++r) {
-            if (j == me) {
-                c->mesh_peer[r][j] = c->mesh_reg[r];
-                continue;
-            }
-            if (rc) continue;
-            void *p = NULL;
-            e = hipIpcOpenMemHandle(&p, all[j].h[r], hipIpcMemLazyEnablePeerAccess);
-            if (e != hipSuccess) rc = inccl_hip_check(e, "mesh: hipIpcOpenMemHandle");
-            c->mesh_peer[r][j] = (char *)p;
-        }
-    free(all);
-    /* agree on the outcome, so that every rank falls back alike */
-    int32_t mine_rc = rc ? 1 : 0, all_rc[INCCL_MAX_LOCAL_INPUTS];
-    MTRACE("mesh peers mapped (rc %d): agree", rc);
-    int rc2 = inccl_boot_allgather(g, &mine_rc, all_rc, sizeof(int32_t));
-    if (rc2) {
-        inccl_mesh_release(c);
-        inccl_mesh_release(&old);
-        return rc2;
-    }
-    for (int j = 0; j < W; ++j)
-        if (all_rc[j]) {
-            if (!rc) rc = inccl_set_error(INCCL_ERR_HIP, "mesh: rank %d could not map the peer buffers", j);
-            inccl_mesh_release(c);
-            inccl_mesh_release(&old);
-            return rc;
-        }
-    /* every peer has mapped the new buffers: the old ones can go */
-    if (old.mesh_buf) {
-        int rc_b = inccl_boot_barrier(g);
-        inccl_mesh_release(&old);
-        MTRACE("mesh: old buffers released");
-        if (rc_b) return rc_b;
+    /* four separate regions, so that no single IPC export reaches 2 GiB for
+     * buckets up to ~2 GiB at any W; all polled by the running kernel, the flags
+     * and counters of region 0 start at zero */
+    struct inccl_ipc_region regions[INCCL_MESH_REGIONS];
+    for (int r = 0; r < INCCL_MESH_REGIONS; ++r)
+        regions[r] = (struct inccl_ipc_region){mesh_region_bytes(r, W, cap), 1, r == 0 ? MESH_DATA_OFFSET : 0};
+    /* a regrow replaces the error words (mesh_piece has read the old ones) */
+    rc = inccl_err_words_create(&c->mesh_err_host, &c->mesh_err_dev, 32);
+    rc = inccl_ipc_set_replace(g, &c->mesh_ipc, regions, INCCL_MESH_REGIONS, rc, "mesh");
+    if (rc) {
+        inccl_mesh_release(c);   /* back to a clean state: the next call starts over */
+        return rc;
     }
     c->mesh_cap = cap;
     c->mesh_grid = grid;
@@ -240,7 +162,7 @@ static void mesh_flag_census(struct inccl_communicator *c, uint32_t e, uint32_t 
     int cnt[4][INCCL_MAX_LOCAL_INPUTS];
     memset(cnt, 0xff, sizeof(cnt));   /* -1: not read */
     for (int j = 0; j < W && j < INCCL_MAX_LOCAL_INPUTS; ++j) {
-        const uint32_t *own = (const uint32_t *)c->mesh_buf, *peer = (const uint32_t *)c->mesh_peer[0][j];
+        const uint32_t *own = (const uint32_t *)c->mesh_ipc.own[0], *peer = (const uint32_t *)c->mesh_ipc.peer[0][j];
         const uint32_t *src[4] = {own + (size_t)j * INCCL_MESH_MAX_CHUNKS,
                                   own + (size_t)(INCCL_MAX_LOCAL_INPUTS + j) * INCCL_MESH_MAX_CHUNKS,
                                   peer ? peer + (size_t)me * INCCL_MESH_MAX_CHUNKS : NULL,
@@ -272,7 +194,7 @@ static int mesh_piece(struct inccl_communicator *c, int kind16, const void *cons
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     INCCL_HIP(hipStreamIsCapturing(st, &cap));
     const int capturing = cap != hipStreamCaptureStatusNone;
-    if (capturing && (!c->mesh_buf || c->mesh_cap < shard))   /* collective setup cannot run in a capture */
+    if (capturing && (!c->mesh_ipc.own[0] || c->mesh_cap < shard))   /* collective setup cannot run in a capture */
         return inccl_set_error(INCCL_ERR_STATE, "mesh: make one call of this size outside graph capture first");
     /* an earlier call's failure is reported before anything else, a regrow
      * included (it would replace the error words) */
@@ -328,18 +250,18 @@ static int mesh_piece(struct inccl_communicator *c, int kind16, const void *cons
     l.lag = lag;
     l.grid = c->mesh_grid;
     for (int j = 0; j < W; ++j) {
-        l.peer_sig[j] = (uint32_t *)c->mesh_peer[0][j];
-        l.peer_inbox[j] = (uint32_t *)c->mesh_peer[1][j];
-        l.peer_res[j] = (const uint32_t *)c->mesh_peer[2][j];
-        l.peer_resin[j] = (uint32_t *)c->mesh_peer[3][j];
+        l.peer_sig[j] = (uint32_t *)c->mesh_ipc.peer[0][j];
+        l.peer_inbox[j] = (uint32_t *)c->mesh_ipc.peer[1][j];
+        l.peer_res[j] = (const uint32_t *)c->mesh_ipc.peer[2][j];
+        l.peer_resin[j] = (uint32_t *)c->mesh_ipc.peer[3][j];
     }
     l.own_resin = l.peer_resin[me];
     l.push_res = c->mesh_push;
     l.rs = rs;
     l.own_inbox = l.peer_inbox[me];
     l.own_res = (uint32_t *)l.peer_res[me];
-    l.own_sig = (const uint32_t *)c->mesh_buf;
-    l.ctr = (uint32_t *)(c->mesh_buf + MESH_CTR_OFFSET);
+    l.own_sig = (const uint32_t *)c->mesh_ipc.own[0];
+    l.ctr = (uint32_t *)(c->mesh_ipc.own[0] + MESH_CTR_OFFSET);
     l.err = c->mesh_err_dev;
     l.W = W;
     l.me = me;

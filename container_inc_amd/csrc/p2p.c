@@ -1,8 +1,8 @@
 /* p2p.c -- the "p2p" exchange engine: reduce-scatter and all-gather as direct
  * peer reads over xGMI with this library's own kernels (no RCCL on the data path).
  *
- * Every rank owns two library-allocated device buffers whose HIP IPC handles are
- * exchanged once over the group's bootstrap sockets:
+ * Every rank owns two library-allocated device buffers that every peer maps over
+ * HIP IPC (one buffer set, created and regrown by ipc.c):
  *   part  int32 [W * shard]  this rank's quantised local sums (W shards)
  *   res   fp32  [W * shard]  this rank's dequantised result shard at rank * shard
  * One bucket piece:
@@ -29,52 +29,9 @@
 #include "inccl_internal.h"
 #include "inccl_kernels.h"
 
-typedef struct {
-    hipIpcMemHandle_t part, res;
-} p2p_handles;
-
-/* $INCCL_TRACE: every (re)growth logs, per rank, the FNV-1a hash of each
- * exported handle and the base address each peer's buffer mapped to, so that
- * a mapping that resolves to an earlier export (same base as before while the
- * handle changed) is visible in the log */
-static uint64_t handle_hash(const hipIpcMemHandle_t *h)
-{
-    const unsigned char *b = (const unsigned char *)h;
-    uint64_t x = 1469598103934665603ull;
-    for (size_t i = 0; i < sizeof(*h); ++i) x = (x ^ b[i]) * 1099511628211ull;
-    return x;
-}
-
-static void p2p_trace(const struct inccl_communicator *c, const char *what, const p2p_handles *all, int W)
-{
-    if (!getenv("INCCL_TRACE")) return;
-    char line[2048];
-    int k = snprintf(line, sizeof(line), "[inccl p2p rank %d] %s cap %zu own part %p res %p", c->group->rank, what,
-                     c->p2p_cap, (void *)c->p2p_part, (void *)c->p2p_res);
-    for (int j = 0; j < W && k > 0 && (size_t)k < sizeof(line); ++j)
-        k += snprintf(line + k, sizeof(line) - (size_t)k, " | peer %d handle %016llx/%016llx -> part %p res %p", j,
-                      all ? (unsigned long long)handle_hash(&all[j].part) : 0ull,
-                      all ? (unsigned long long)handle_hash(&all[j].res) : 0ull, (void *)c->p2p_peer_part[j],
-                      (void *)c->p2p_peer_res[j]);
-    fprintf(stderr, "%s\n", line);   /* one write per line: ranks share the log */
-}
-
 void inccl_p2p_release(struct inccl_communicator *c)
 {
-    const int W = c->group->world_size, me = c->group->rank;
-    if (c->p2p_cap == 0 && !c->p2p_part) return;
-    hipDeviceSynchronize();
-    for (int j = 0; j < W && j < INCCL_MAX_LOCAL_INPUTS; ++j) {
-        if (j == me) continue;
-        if (c->p2p_peer_part[j]) hipIpcCloseMemHandle(c->p2p_peer_part[j]);
-        if (c->p2p_peer_res[j]) hipIpcCloseMemHandle(c->p2p_peer_res[j]);
-        c->p2p_peer_part[j] = NULL;
-        c->p2p_peer_res[j] = NULL;
-    }
-    if (c->p2p_part) hipFree(c->p2p_part);
-    if (c->p2p_res) hipFree(c->p2p_res);
-    c->p2p_part = NULL;
-    c->p2p_res = NULL;
+    inccl_ipc_set_release(c->group, &c->p2p_ipc);
     c->p2p_cap = 0;
 }
 
@@ -82,98 +39,19 @@ void inccl_p2p_release(struct inccl_communicator *c)
 static int p2p_ensure(struct inccl_communicator *c, size_t elems)
 {
     struct inccl_group *g = c->group;
-    const int W = g->world_size, me = g->rank;
-    if (c->p2p_cap >= elems && c->p2p_part) return 0;
+    if (c->p2p_cap >= elems && c->p2p_ipc.own[0]) return 0;
     if (elems * sizeof(int32_t) > g->ipc_max_bytes)   /* same sizes and bound on every rank: all refuse alike */
         return inccl_set_error(INCCL_ERR_ARG, "p2p: a %zu-element bucket needs %zu-byte IPC buffers; this group's stay "
                                "below %zu bytes (under PyTorch's bundled HSA runtime, importing a larger one hangs; "
                                "runtime.c)", elems, elems * sizeof(int32_t), g->ipc_max_bytes);
-    /* this rank's queued reads of the peers' buffers (the previous call's gather)
-     * drain before anyone may drop them */
-    INCCL_HIP(hipDeviceSynchronize());
-    int rc = inccl_boot_barrier(g);
+    int rc = inccl_boot_shm_init(g);   /* same-node fast barrier for the per-call syncs */
     if (rc) return rc;
-    rc = inccl_boot_shm_init(g);   /* same-node fast barrier for the per-call syncs */
-    if (rc) return rc;
-    /* Make before break: the new buffers are allocated, exported and mapped by
-     * every peer while the old ones are still alive, and the old ones go only
-     * after a barrier.  Freeing first lets a new export reuse the old one's
-     * identity (a dmabuf fd number) while a peer's runtime may still resolve it
-     * to the old import: a regrowth then, intermittently, left one rank reading
-     * a peer's old buffer on every later call. */
-    /* $INCCL_P2P_FREE_FIRST=1 restores the first version's order (free the old
-     * buffers, then allocate and exchange the new ones) -- for the regrowth
-     * regression test only */
-    const char *ff = getenv("INCCL_P2P_FREE_FIRST");
-    if (ff && atoi(ff) != 0 && c->p2p_part) {
-        p2p_trace(c, "free-first: releasing", NULL, W);
-        rc = inccl_boot_barrier(g);
-        if (rc) return rc;
-        inccl_p2p_release(c);
-    }
-    struct inccl_communicator old = *c;
-    c->p2p_part = NULL;
-    c->p2p_res = NULL;
-    c->p2p_cap = 0;
-    for (int j = 0; j < INCCL_MAX_LOCAL_INPUTS; ++j) {
-        c->p2p_peer_part[j] = NULL;
-        c->p2p_peer_res[j] = NULL;
-    }
-    size_t cap = (elems + (1u << 19) - 1) & ~(size_t)((1u << 19) - 1);   /* 2 MiB granules */
-    p2p_handles mine, *all = (p2p_handles *)calloc((size_t)W, sizeof(p2p_handles));
-    if (!all) {
-        inccl_p2p_release(&old);
-        return inccl_set_error(INCCL_ERR_NOMEM, "p2p: out of memory");
-    }
-    memset(&mine, 0, sizeof(mine));
-    /* local failures are carried to the collective outcome check below */
-    hipError_t e = hipMalloc((void **)&c->p2p_part, cap * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&c->p2p_res, cap * sizeof(float));
-    if (e == hipSuccess) {
-        c->p2p_cap = cap;
-        e = hipIpcGetMemHandle(&mine.part, c->p2p_part);
-        if (e == hipSuccess) e = hipIpcGetMemHandle(&mine.res, c->p2p_res);
-    }
-    if (e != hipSuccess) rc = inccl_hip_check(e, "p2p: hipMalloc/hipIpcGetMemHandle");
-    int rc_x = inccl_boot_allgather(g, &mine, all, sizeof(p2p_handles));
-    if (rc_x) {
-        free(all);
-        inccl_p2p_release(&old);
-        return rc_x;
-    }
-    for (int j = 0; rc == 0 && j < W; ++j) {
-        if (j == me) {
-            c->p2p_peer_part[j] = c->p2p_part;
-            c->p2p_peer_res[j] = c->p2p_res;
-            continue;
-        }
-        void *pp = NULL, *pr = NULL;
-        e = hipIpcOpenMemHandle(&pp, all[j].part, hipIpcMemLazyEnablePeerAccess);
-        if (e == hipSuccess) e = hipIpcOpenMemHandle(&pr, all[j].res, hipIpcMemLazyEnablePeerAccess);
-        if (e != hipSuccess) rc = inccl_hip_check(e, "hipIpcOpenMemHandle");
-        c->p2p_peer_part[j] = (int32_t *)pp;
-        c->p2p_peer_res[j] = (float *)pr;
-    }
-    p2p_trace(c, "mapped", all, W);
-    free(all);
-    /* every peer has mapped the new buffers: the old ones can go */
-    int rc_b = inccl_boot_barrier(g);
-    inccl_p2p_release(&old);
-    if (rc_b) return rc_b;
-    /* agree on the outcome: a rank whose IPC mapping failed must not leave its
-     * peers waiting in a barrier it never reaches, and everyone must see the
-     * failure so the caller can fall back on every rank alike */
-    int32_t mine_rc = rc ? 1 : 0, all_rc[64];
-    if (W > 64) return inccl_set_error(INCCL_ERR_ARG, "p2p: world too large");
-    int rc2 = inccl_boot_allgather(g, &mine_rc, all_rc, sizeof(int32_t));
-    if (rc2) return rc2;
-    for (int j = 0; j < W; ++j)
-        if (all_rc[j]) {
-            if (!rc) rc = inccl_set_error(INCCL_ERR_HIP, "p2p: rank %d could not map the peer buffers", j);
-            inccl_p2p_release(c);
-            return rc;
-        }
-    return 0;
+    const size_t cap = (elems + (1u << 19) - 1) & ~(size_t)((1u << 19) - 1);   /* 2 MiB granules */
+    /* read after a kernel boundary and a barrier, never polled: plain hipMalloc */
+    const struct inccl_ipc_region regions[2] = {{cap * sizeof(int32_t), 0, 0}, {cap * sizeof(float), 0, 0}};
+    rc = inccl_ipc_set_replace(g, &c->p2p_ipc, regions, 2, 0, "p2p");
+    c->p2p_cap = rc ? 0 : cap;
+    return rc;
 }
 
 static int sync_and_barrier(struct inccl_communicator *c, hipStream_t st)
@@ -209,25 +87,26 @@ static int p2p_exchange(struct inccl_communicator *c, int in_kind, const void *c
     if (!gather && (total != n || (shard & 3))) return inccl_set_error(INCCL_ERR_ARG, "p2p reduce-scatter: bad shard");
     int rc = p2p_ensure(c, total);
     if (rc) return rc;
+    int32_t *part = (int32_t *)c->p2p_ipc.own[0];
     /* the previous call's gather may still be reading the peers' result shards,
      * which the peers rewrite once this call's first barrier has passed: order
      * it before that barrier's host sync when the caller switches streams */
     if (c->p2p_last_stream && c->p2p_last_stream != st) INCCL_HIP(hipStreamWaitEvent(st, c->ev[8], 0));
     /* 1. fill part */
     if (in_kind == INCCL_KIND_Q32) {
-        INCCL_HIP(hipMemcpyAsync(c->p2p_part, srcs[0], n * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+        INCCL_HIP(hipMemcpyAsync(part, srcs[0], n * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
     } else {
-        rc = inccl_k_stream(in_kind, INCCL_KIND_Q32, srcs, R, c->p2p_part, n, sc->k, sc->amax, sc->R, 0, st);
+        rc = inccl_k_stream(in_kind, INCCL_KIND_Q32, srcs, R, part, n, sc->k, sc->amax, sc->R, 0, st);
         if (rc) return inccl_set_error(INCCL_ERR_HIP, "p2p %squant+sum launch failed (%d)",
                                        gather ? what : "reduce-scatter ", rc);
     }
-    if (total > n) INCCL_HIP(hipMemsetAsync(c->p2p_part + n, 0, (total - n) * sizeof(int32_t), st));
+    if (total > n) INCCL_HIP(hipMemsetAsync(part + n, 0, (total - n) * sizeof(int32_t), st));
     rc = sync_and_barrier(c, st);
     if (rc) return rc;
     /* 3. pull shard `me` from every peer, sum, dequantise */
     const void *peer[INCCL_MAX_LOCAL_INPUTS];
-    for (int j = 0; j < W; ++j) peer[j] = c->p2p_peer_part[j] + (size_t)me * shard;
-    rc = inccl_k_peer_reduce(out_kind, peer, W, gather ? (void *)((char *)c->p2p_res + (size_t)me * shard * es) : dst,
+    for (int j = 0; j < W; ++j) peer[j] = (const int32_t *)c->p2p_ipc.peer[0][j] + (size_t)me * shard;
+    rc = inccl_k_peer_reduce(out_kind, peer, W, gather ? (void *)(c->p2p_ipc.own[1] + (size_t)me * shard * es) : dst,
                              shard, sc->k, sc->amax, sc->R, out_kind == INCCL_KIND_Q32 ? 0 : c->out_shift, st);
     if (rc) return inccl_set_error(INCCL_ERR_HIP, "p2p %sreduce-scatter launch failed (%d)", what, rc);
     rc = sync_and_barrier(c, st);
@@ -238,7 +117,7 @@ static int p2p_exchange(struct inccl_communicator *c, int in_kind, const void *c
         int64_t off[INCCL_MAX_LOCAL_INPUTS], cnt[INCCL_MAX_LOCAL_INPUTS];
         for (int j = 0; j < W; ++j) {
             const size_t lo = (size_t)j * shard;
-            src[j] = (const char *)c->p2p_peer_res[j] + lo * es;
+            src[j] = c->p2p_ipc.peer[1][j] + lo * es;
             off[j] = (int64_t)lo;
             cnt[j] = lo >= n ? 0 : (int64_t)((n - lo) < shard ? (n - lo) : shard);
         }

@@ -13,7 +13,7 @@ B=container_inc_amd/obj_asan
 mkdir -p $B
 SAN="-fsanitize=address,undefined -fno-omit-frame-pointer -g"
 CF="-O1 -std=c11 -fPIC -Wall -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude -I$CSRC $SAN"
-for f in api bootstrap transport p2p ll mesh switch copypool hostdma runtime; do
+for f in api bootstrap transport p2p ll mesh ipc switch copypool hostdma runtime; do
   gcc $CF -c $CSRC/$f.c -o $B/$f.o || exit 4
 done
 # linked by gcc, whose sanitizer runtime the host objects were built for; the
