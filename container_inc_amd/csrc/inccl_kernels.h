@@ -87,8 +87,10 @@ struct inccl_ll_launch {
     int out_shift;                                     /* dequantise with 2^-(k + out_shift) */
     size_t rs_lo, rs_n;                                /* rs_n > 0: reduce-scatter -- dst = elements
                                                         * [rs_lo, rs_lo + rs_n) of the result (both % 4 == 0) */
+    int grid;                                          /* workgroups: inccl_k_ll_grid(n), the same on every rank */
 };
 int inccl_k_ll_grid(size_t n);
+int inccl_k_ll_protocol_wt(void);   /* 1: the wt protocol, 0: fence ($INCCL_LL_PROTOCOL) */
 int inccl_k_ll_oneshot(const struct inccl_ll_launch *l, void *stream);
 
 /* the one-kernel large-bucket allreduce (inccl_mesh.hip): push reduce-scatter,

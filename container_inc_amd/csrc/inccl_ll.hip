@@ -36,6 +36,18 @@
 #include "inccl_launch.h"
 #include "inccl_stream.h"
 
+// The protocol every launch of this process takes ($INCCL_LL_PROTOCOL: "wt",
+// the default, or "fence"; same on every rank): 1 = wt, 0 = fence.
+extern "C" int inccl_k_ll_protocol_wt(void)
+{
+    static int wt = -1;
+    if (wt < 0) {
+        const char* e = getenv("INCCL_LL_PROTOCOL");
+        wt = (e && e[0] == 'f') ? 0 : 1;
+    }
+    return wt;
+}
+
 namespace {
 
 using namespace inccl_dev;
@@ -218,12 +230,7 @@ __global__ __launch_bounds__(kLLBlock) void k_ll_oneshot(LLArgs a, int vec_src, 
 template <int R>
 hipError_t launch_R(const LLArgs& a, int grid, int vs, int vd, hipStream_t st)
 {
-    static int wt = -1;   // $INCCL_LL_PROTOCOL: "wt" (default) or "fence"; same on every rank
-    if (wt < 0) {
-        const char* e = getenv("INCCL_LL_PROTOCOL");
-        wt = (e && e[0] == 'f') ? 0 : 1;
-    }
-    if (wt) hipLaunchKernelGGL((k_ll_oneshot<R, true>), dim3(grid), dim3(kLLBlock), 0, st, a, vs, vd);
+    if (inccl_k_ll_protocol_wt()) hipLaunchKernelGGL((k_ll_oneshot<R, true>), dim3(grid), dim3(kLLBlock), 0, st, a, vs, vd);
     else hipLaunchKernelGGL((k_ll_oneshot<R, false>), dim3(grid), dim3(kLLBlock), 0, st, a, vs, vd);
     return hipGetLastError();
 }
@@ -248,7 +255,8 @@ extern "C" int inccl_k_ll_grid(size_t n)
 
 extern "C" int inccl_k_ll_oneshot(const struct inccl_ll_launch* l, void* stream)
 {
-    if (!l || l->R < 1 || l->R > kMaxR || l->W < 2 || l->W > kMaxR || l->me < 0 || l->me >= l->W ||
+    if (!l || l->grid < 1 || l->grid > INCCL_LL_MAX_BLOCKS || l->R < 1 || l->R > kMaxR || l->W < 2 ||
+        l->W > kMaxR || l->me < 0 || l->me >= l->W ||
         (l->rs_n && ((l->rs_lo | l->rs_n) & 3u || l->rs_lo + l->rs_n > l->n)))
         return INCCL_ERR_ARG;
     LLArgs a{};
@@ -276,7 +284,7 @@ extern "C" int inccl_k_ll_oneshot(const struct inccl_ll_launch* l, void* stream)
     int vs = 1;
     for (int r = 0; r < l->R; ++r) vs &= aligned16(l->src[r]) ? 1 : 0;
     const int vd = aligned16(l->dst) ? 1 : 0;
-    const int grid = inccl_k_ll_grid(l->n);
+    const int grid = l->grid;
     hipStream_t st = (hipStream_t)stream;
     hipError_t e;
 #define INCCL_CALL(RR) e = launch_R<RR>(a, grid, vs, vd, st)

@@ -104,6 +104,7 @@ int inccl_ll_piece(struct inccl_communicator *c, const float *const *srcs, int R
     l.out_shift = c->out_shift;
     l.rs_lo = rs_lo;
     l.rs_n = rs_n;
+    l.grid = inccl_k_ll_grid(n);
     /* the parity argument needs this rank's calls in order: chain across streams
      * (inside a graph capture the caller's single capture stream orders them) */
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
@@ -119,6 +120,9 @@ int inccl_ll_piece(struct inccl_communicator *c, const float *const *srcs, int R
         INCCL_HIP(hipStreamSynchronize(st));
         INCCL_HIP(hipMemcpy(before, l.ctr, sizeof(before), hipMemcpyDeviceToHost));
     }
+    if (getenv("INCCL_TRACE"))   /* one line per launch (debugging aid), as mesh.c's: the grid launched */
+        fprintf(stderr, "[inccl %d] ll launch n %zu grid %d protocol %s\n", me, n, l.grid,
+                inccl_k_ll_protocol_wt() ? "wt" : "fence");
     rc = inccl_k_ll_oneshot(&l, st);
     if (rc) return inccl_set_error(INCCL_ERR_HIP, "ll kernel launch failed (%d)", rc);
     if (!capturing) {
@@ -130,7 +134,7 @@ int inccl_ll_piece(struct inccl_communicator *c, const float *const *srcs, int R
         INCCL_HIP(hipMemcpy(after, l.ctr, sizeof(after), hipMemcpyDeviceToHost));
         if (after[0] != before[0] + 1 || before[1] != 0 || after[1] != 0)
             fprintf(stderr, "[inccl ll rank %d] n %zu grid %d: call counter %u -> %u, retired %u -> %u\n", me, n,
-                    inccl_k_ll_grid(n), before[0], after[0], before[1], after[1]);
+                    l.grid, before[0], after[0], before[1], after[1]);
     }
     return 0;
 }
