@@ -1306,7 +1306,9 @@ __global__ __launch_bounds__(kWave* kNrSumWaves) void k_nr_sum(InccSwitchState s
 constexpr int kEgressWaves = 16;
 // input frames per wave at a time: 4 up to fan-in 8; 16 above, where most
 // chunks of 4 would hold no completing frame (fan-in 16: 48.3 us with 4, 43.0
-// with 16; fan-in 5: 29.2 with 4, 32.3 with 16)
+// with 16; fan-in 5: 29.2 with 4, 32.3 with 16).  tests/test_gpu_switch_guards.py
+// copies this rule (_egress_chunk) to give every case a partial last chunk:
+// change both together
 __host__ __device__ constexpr uint32_t egress_chunk(int fan)
 {
     return fan <= 8 ? 4u : 16u;

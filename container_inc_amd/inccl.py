@@ -795,13 +795,15 @@ def _frames_arg(frames, name="frames"):
     return _dev_ptr(frames, torch.uint8, name), frames.shape[0], frames.shape[1]
 
 
-def icrc_frames(frames, stream=None):
-    """ICRC (util.c:250-286) of every frame row; returns an int32 tensor of the uint32 values."""
+def icrc_frames(frames, stream=None, out=None):
+    """ICRC (util.c:250-286) of every frame row; returns an int32 tensor of the
+    uint32 values (`out`, if one is passed in: at least `count` int32)."""
     torch = _torch()
     ptr, count, stride = _frames_arg(frames)
-    out = torch.empty(count, dtype=torch.int32, device=frames.device)
-    check(load().inccl_icrc_frames(ptr, stride, count, _dev_ptr(out, torch.int32, "out"), _stream_handle(stream)),
-          "inccl_icrc_frames")
+    if out is None:
+        out = torch.empty(count, dtype=torch.int32, device=frames.device)
+    check(load().inccl_icrc_frames(ptr, stride, count, _dev_ptr(out, torch.int32, "out", count),
+                                   _stream_handle(stream)), "inccl_icrc_frames")
     return out
 
 
@@ -826,13 +828,17 @@ class GpuSwitch:
     def reset(self, stream=None):
         check(load().inccl_switch_reset(self.handle, _stream_handle(stream)), "inccl_switch_reset")
 
-    def ingress(self, frames, ports, stream=None):
+    def ingress(self, frames, ports, stream=None, action=None, psn=None):
         torch = _torch()
         ptr, count, stride = _frames_arg(frames)
         pp = _dev_ptr(ports, torch.int32, "ports", count)
-        action = torch.empty(count, dtype=torch.int32, device=frames.device)
-        psn = torch.empty(count, dtype=torch.int32, device=frames.device)
-        check(load().inccl_switch_ingress(self.handle, ptr, stride, count, pp, action.data_ptr(), psn.data_ptr(),
+        if action is None:
+            action = torch.empty(count, dtype=torch.int32, device=frames.device)
+        if psn is None:
+            psn = torch.empty(count, dtype=torch.int32, device=frames.device)
+        check(load().inccl_switch_ingress(self.handle, ptr, stride, count, pp,
+                                          _dev_ptr(action, torch.int32, "action", count),
+                                          _dev_ptr(psn, torch.int32, "psn", count),
                                           _stream_handle(stream)), "inccl_switch_ingress")
         return action, psn
 

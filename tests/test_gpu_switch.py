@@ -17,12 +17,18 @@ STRIDE = 1152
 INT32_MIN, INT32_MAX = -(2 ** 31), 2 ** 31 - 1
 
 
-def _rows(frames, dev, stride=STRIDE):
-    import torch
+def _rows_host(frames, stride=STRIDE):
+    """The frames as rows of `stride` bytes: zero-padded, or cut off at the row's end."""
     a = np.zeros((len(frames), stride), np.uint8)
     for i, f in enumerate(frames):
+        f = f[:stride]
         a[i, : len(f)] = np.frombuffer(f, np.uint8)
-    return torch.from_numpy(a).to(dev)
+    return a
+
+
+def _rows(frames, dev, stride=STRIDE):
+    import torch
+    return torch.from_numpy(_rows_host(frames, stride)).to(dev)
 
 
 def test_icrc_golden_frame(gpu):
@@ -88,11 +94,12 @@ def test_icrc_row_strides_odd_counts(gpu, orc, stride, count):
 MODES = ["split", "batch"]
 
 
-def _run(sw, mode, fr, pt, tmpl_dev, out_stride=STRIDE, stream=None, out=None, out_len=None):
+def _run(sw, mode, fr, pt, tmpl_dev, out_stride=STRIDE, stream=None, out=None, out_len=None, action=None, psn=None):
     """One batch through the switch either way: (action, psn, out, out_len)."""
     if mode == "batch":
-        return sw.batch(fr, pt, tmpl_dev, out_stride=out_stride, stream=stream, out=out, out_len=out_len)
-    action, psn = sw.ingress(fr, pt, stream=stream)
+        return sw.batch(fr, pt, tmpl_dev, out_stride=out_stride, stream=stream, out=out, out_len=out_len,
+                        action=action, psn=psn)
+    action, psn = sw.ingress(fr, pt, stream=stream, action=action, psn=psn)
     out, out_len = sw.egress(fr, pt, action, psn, tmpl_dev, out_stride=out_stride, stream=stream, out=out,
                              out_len=out_len)
     return action, psn, out, out_len
